@@ -11,6 +11,11 @@ value = whole-job virtual clients trained per second (aggregate over
 all ranks); rounds/sec is value / clients_per_round.
 
 Run:  python bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints one JSON
+result line; `--dump-outputs DIR` also writes the last timed round's
+outputs as DIR/<name>.npy (same arguments -> same inputs, so two builds
+compare output for output).  Measurements beyond the headline figure
+belong behind `--full`.
 For N>1 the driver launches it under torch.distributed.run with one
 rank per GPU (RANK/LOCAL_RANK/WORLD_SIZE read from the env).
 """
@@ -93,6 +98,39 @@ PRESETS = {
 }
 
 
+# --dump-outputs keeps the global model whole up to this many elements
+# (fp32: 48 MB) and writes a fixed seeded sample of a larger one
+DUMP_MAX_ELEMS = 12 * 1000 * 1000
+DUMP_SAMPLE_SEED = 20240229
+
+
+def _dump_outputs(out_dir: str, eng, record, rank: int) -> None:
+    """Write what the last timed round handed back: the aggregated
+    global model (what a caller reads from the engine after the round)
+    and the round's client counts, as <name>.npy."""
+    import numpy as np
+    eng._finish_aggregate()       # multi-rank: fold the in-flight reduce
+    if rank != 0 or record is None:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    flat = eng.master.flat.detach().float()
+    n = flat.numel()
+    if n > DUMP_MAX_ELEMS:
+        gen = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randperm(n, generator=gen)[:DUMP_MAX_ELEMS]
+        idx = idx.sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(out_dir, "global_params.npy"),
+            flat.cpu().numpy().astype(np.float32))
+    counts = [record["round"], record["success"], record["failed"],
+              record["trained"], int(record["round_failed"])]
+    np.save(os.path.join(out_dir, "round_counts.npy"),
+            np.asarray(counts, dtype=np.float64))
+    if record.get("loss") is not None:
+        np.save(os.path.join(out_dir, "round_loss.npy"),
+                np.asarray([record["loss"]], dtype=np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -112,6 +150,15 @@ def main() -> int:
     ap.add_argument("--op-stacks", default="",
                     help="write key_averages grouped by python stack "
                          "(slow; finds which call site owns a kernel)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed "
+                         "round produced (global model, round counts) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks beyond the "
+                         "headline figure (none exist yet: a plain run does "
+                         "only setup, warmup, the timed steps and the result "
+                         "line; anything added later goes behind this flag)")
     args = ap.parse_args()
 
     preset = dict(PRESETS[args.preset])
@@ -124,7 +171,7 @@ def main() -> int:
         preset["batch_size"] = args.batch
 
     use_gpu = torch.cuda.is_available() and not force_cpu
-    ctx = pdist.init_distributed()
+    ctx = pdist.init_distributed("cpu" if force_cpu else None)
     world = max(1, ctx.world_size)
 
     job = EngineJob(
@@ -164,11 +211,15 @@ def main() -> int:
         profiler.__enter__()
 
     t0 = time.perf_counter()
+    record = None
     for r in range(args.warmup, args.warmup + args.steps):
-        eng.run_round(r)
+        record = eng.run_round(r)
     pdist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, eng, record, ctx.rank)
 
     if profiler is not None:
         profiler.__exit__(None, None, None)

@@ -13,7 +13,8 @@ this CLI plays that role on one node:
 
 `submit/status/stop/queue` talk to a running server when `--server
 http://host:port` is given, otherwise they run a one-shot in-process
-session over the persistent data directory.
+session over the persistent data directory.  A plain `submit` only
+queues the task there; `submit --wait` or `serve` runs what is queued.
 """
 
 from __future__ import annotations
@@ -24,10 +25,15 @@ import sys
 import time
 
 
-def _session(args):
+def _session(args, threads: bool = False):
+    """One-shot commands only read or edit the persisted tables, so they
+    start no manager threads: a scheduler thread would launch the queued
+    task's engine in a process that is about to exit, which orphans the
+    task and can abort the exit while the engine thread is in native
+    code.  Only `serve` and `submit --wait` run tasks."""
     from .session import SimulatorSession
     return SimulatorSession(svc=0, data_dir=args.data_dir or None,
-                            auto_start_threads=True)
+                            auto_start_threads=threads)
 
 
 def _http(args, method: str, path: str, body=None):
@@ -42,7 +48,7 @@ def _http(args, method: str, path: str, body=None):
 
 
 def cmd_serve(args) -> int:
-    sess = _session(args)
+    sess = _session(args, threads=True)
     print(f"serving JSON API on {args.host}:{args.port} (svc={sess.svc})")
     sess.serve(host=args.host, port=args.port, block=True)
     return 0
@@ -55,7 +61,7 @@ def cmd_submit(args) -> int:
         out = _http(args, "POST", "/taskmgr/submitTask", {"task": task})
         print(json.dumps(out))
         return 0 if out.get("is_success") else 1
-    sess = _session(args)
+    sess = _session(args, threads=args.wait)
     ok, msg = sess.task_mgr.submit_task(json.dumps(task))
     print(json.dumps({"is_success": ok, "message": msg}))
     if not ok:

@@ -48,7 +48,9 @@ def init_distributed(device: Optional[str] = None,
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(rank)))
-    use_gpu = torch.cuda.is_available()
+    # an explicit CPU device keeps the group on gloo even on a GPU host
+    use_gpu = torch.cuda.is_available() and \
+        (device is None or str(device).startswith("cuda"))
     if device is None:
         device = f"cuda:{local_rank}" if use_gpu else "cpu"
     if world <= 1:

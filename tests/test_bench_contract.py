@@ -62,6 +62,40 @@ def test_bench_two_rank_torchrun_contract():
     assert len(json_lines) == 1
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed round's outputs as .npy
+    (float32/float64, <= 64 MB in all); the same arguments give the same
+    inputs, so two runs agree.  --full is accepted and keeps the result
+    line's meaning."""
+    import numpy as np
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--preset", "mlp-cpu",
+             "--steps", "2", "--warmup", "1", "--dump-outputs", str(d),
+             *extra],
+            cwd=REPO, capture_output=True, text=True, timeout=240)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = last_json_line(out.stdout)
+        assert REQUIRED_KEYS.issubset(line.keys())
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert "global_params.npy" in files and "round_counts.npy" in files
+        assert all(f.endswith(".npy") for f in files)
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 * 2 ** 20
+        dumps.append({f: np.load(d / f) for f in files})
+    a, b = dumps
+    assert a.keys() == b.keys()
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64)
+        assert np.isfinite(a[f]).all()
+        np.testing.assert_array_equal(a[f], b[f])
+    # last timed round = warmup + steps - 1; all 10 clients trained
+    assert a["round_counts.npy"].tolist() == [2.0, 10.0, 0.0, 10.0, 0.0]
+    assert a["global_params.npy"].size > 0
+
+
 def test_bench_trace_flag_writes_chrome_trace(tmp_path):
     import subprocess, sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

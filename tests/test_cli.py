@@ -10,6 +10,8 @@ import sys
 
 from tests.test_manager import task_json
 
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 def _run(tmp, *args, inp=None):
     env = dict(os.environ)
@@ -18,7 +20,7 @@ def _run(tmp, *args, inp=None):
         [sys.executable, "-m", "olearning_sim_amd",
          "--data-dir", str(tmp / "data"), *args],
         capture_output=True, text=True, timeout=180, env=env,
-        cwd="/root/repo")
+        cwd=REPO)
 
 
 def test_cli_submit_status_queue(tmp_path):

@@ -82,6 +82,16 @@ def wait_terminal(mgr, task_id, timeout=30.0):
     return mgr.get_task_status(task_id)
 
 
+def two_rank_group_env(monkeypatch):
+    """A 2-rank worker group takes one GPU per rank.  On a host with a
+    single GPU the ranks cannot both have one, so hide the GPU from the
+    worker processes: they then run the gloo-on-CPU path these
+    control-plane tests describe, as on a host with no GPU at all."""
+    import torch
+    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
+        monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")
+
+
 def test_submit_validates_and_queues():
     mgr = make_manager()
     ok, msg = mgr.submit_task(task_json())
@@ -470,13 +480,14 @@ def test_orphaned_running_task_fails_on_restart(tmp_path):
     mgr2.shutdown()
 
 
-def test_submit_routes_multi_gpu_task_to_worker_group(tmp_path):
+def test_submit_routes_multi_gpu_task_to_worker_group(tmp_path, monkeypatch):
     """A task whose train operator asks num_gpus > 1 runs as a worker
     group (one process per device, torchrun; gloo on CPU) launched via
     the NodeClusterManager, and its result rows fuse to SUCCEEDED
     (reference TaskRunner submits to the Ray fabric,
     task_runner.py:41-87)."""
     from olearning_sim_amd.cluster.node_manager import NodeClusterManager
+    two_rank_group_env(monkeypatch)
     table = TaskTableRepo(":memory:")
     res = ResourceManager(":memory:", totals={"cpu": 8.0, "mem": 64.0,
                                               "gpu": 0, "hbm_gb": 0})

@@ -10,7 +10,7 @@ from fastapi.testclient import TestClient
 from olearning_sim_amd.session import SimulatorSession
 from olearning_sim_amd.api.server import build_app
 
-from test_manager import task_json
+from test_manager import task_json, two_rank_group_env
 
 
 @pytest.fixture
@@ -125,10 +125,11 @@ def test_performance_api(client, session):
 
 
 @pytest.mark.timeout(420)
-def test_cluster_manager_launches_distributed_worker(tmp_path):
+def test_cluster_manager_launches_distributed_worker(tmp_path, monkeypatch):
     """NodeClusterManager runs the engine worker group (2 CPU ranks over
     gloo) — the control-plane path to multi-GPU execution."""
     import json as _json
+    two_rank_group_env(monkeypatch)
     from olearning_sim_amd.cluster import NodeClusterManager, WorkerGroupSpec
     job = {"task_id": "grp_job", "model_name": "mlp",
            "model_kwargs": {"in_features": 16, "hidden": 8, "num_classes": 4},
