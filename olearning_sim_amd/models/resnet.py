@@ -87,35 +87,46 @@ class ResNet18(ClientBatchedModel):
 
     # -- fast path: client-channel-first layout + hand-written MFMA
     # conv kernels (ops/conv.py / ops/csrc/client_conv.hip) -------------
-    def _block_cbf(self, params: Params, x: torch.Tensor, C: int, pre: str,
-                   stride: int, has_down: bool) -> torch.Tensor:
-        from ..ops.conv import client_conv3x3, client_conv1x1
+    # Activations travel as padded pairs (x, x_pad) (ops/fused.py): every
+    # GroupNorm that feeds a 3x3 conv writes the conv's zero-haloed input
+    # itself; x is the interior view that keeps the autograd graph dense.
+    # x_pad is None wherever a shape falls back to the dense kernels.
+    def _block_cbf(self, params: Params, x: torch.Tensor, x_pad, C: int,
+                   pre: str, stride: int, has_down: bool,
+                   pad_out: bool = True):
+        from ..ops.conv import conv3x3_gn_relu, client_conv1x1
         from ..ops.fused import groupnorm_act
-        h = client_conv3x3(x, params[f"{pre}.c1.w"], stride)
-        h = groupnorm_act(h, C, _GN_GROUPS, params[f"{pre}.gn1.g"],
-                          params[f"{pre}.gn1.b"], relu=True)
-        h = client_conv3x3(h, params[f"{pre}.c2.w"], 1)
+        h, h_pad = conv3x3_gn_relu(x, x_pad, params[f"{pre}.c1.w"], stride,
+                                   C, _GN_GROUPS, params[f"{pre}.gn1.g"],
+                                   params[f"{pre}.gn1.b"])
         if has_down:
-            sc = client_conv1x1(x, params[f"{pre}.down.w"], stride)
+            sc = client_conv1x1(x, params[f"{pre}.down.w"], stride,
+                                x_pad=x_pad)
             sc = groupnorm_act(sc, C, _GN_GROUPS, params[f"{pre}.gndown.g"],
                                params[f"{pre}.gndown.b"])
+            sc_pad = None
         else:
-            sc = x
-        return groupnorm_act(h, C, _GN_GROUPS, params[f"{pre}.gn2.g"],
-                             params[f"{pre}.gn2.b"], res=sc, relu=True)
+            sc, sc_pad = x, x_pad
+        return conv3x3_gn_relu(h, h_pad, params[f"{pre}.c2.w"], 1, C,
+                               _GN_GROUPS, params[f"{pre}.gn2.g"],
+                               params[f"{pre}.gn2.b"], res=sc,
+                               res_pad=sc_pad, pad_out=pad_out)
 
     def forward_cbf(self, params: Params, x: torch.Tensor) -> torch.Tensor:
         from ..ops.conv import client_conv3x3
-        from ..ops.fused import groupnorm_act
+        from ..ops.fused import groupnorm_relu_pad
         C, B = x.shape[0], x.shape[1]
         h = x.permute(0, 2, 1, 3, 4).contiguous()    # [C, 3, B, 32, 32]
         h = client_conv3x3(h, params["stem.w"], 1)
-        h = groupnorm_act(h, C, _GN_GROUPS, params["stem.gn.g"],
-                          params["stem.gn.b"], relu=True)
+        h, h_pad = groupnorm_relu_pad(h, C, _GN_GROUPS, params["stem.gn.g"],
+                                      params["stem.gn.b"])
         for s in range(4):
             stride = 1 if s == 0 else 2
-            h = self._block_cbf(params, h, C, f"s{s}.b0", stride, s > 0)
-            h = self._block_cbf(params, h, C, f"s{s}.b1", 1, False)
+            h, h_pad = self._block_cbf(params, h, h_pad, C, f"s{s}.b0",
+                                       stride, s > 0)
+            # the last block's output feeds the pooling and stays dense
+            h, h_pad = self._block_cbf(params, h, h_pad, C, f"s{s}.b1", 1,
+                                       False, pad_out=s < 3)
         # h: [C, 512, B, 4, 4] -> avg pool -> [C, B, 512]
         h = h.mean(dim=(3, 4)).permute(0, 2, 1)
         return blinear(h, params["fc.w"], params["fc.b"])

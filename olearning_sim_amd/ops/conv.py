@@ -91,6 +91,84 @@ class _Conv3x3PadFn(torch.autograd.Function):
         return dx, dw, None
 
 
+class _Conv3x3GnPadFn(torch.autograd.Function):
+    """One node for conv3x3 -> relu(gn [+ res]) on padded activations.
+
+    Forward: v6 conv on x_pad, then the GroupNorm that writes its output
+    as a padded pair (or dense when pad_out is False).  Backward: the GN
+    backward writes dx dense (wgrad's operand) and again as a padded image
+    (dgrad's operand), so no pad2d pass runs in either direction.  x is
+    the graph-side interior view of x_pad (or the dense tensor x_pad was
+    padded from); it is never read."""
+
+    @staticmethod
+    def forward(ctx, x, x_pad, w, res, res_pad, gamma, beta, clients,
+                groups, eps, stride, pad_out):
+        from .fused import _interior, _res_arg
+        ops = load_hip_ops(required=True)
+        h = ops.conv3x3_fwd_p(x_pad, w, stride)
+        y, mask, mean, rstd = ops.groupnorm_fwd_pad(
+            h, _res_arg(h, res, res_pad), gamma, beta, clients, groups, eps,
+            pad_out)
+        ctx.save_for_backward(x_pad, w, h, mask, mean, rstd, gamma)
+        ctx.meta = (clients, groups, res is not None, stride)
+        # y_pad never has a gradient; do not let autograd zero-fill one
+        ctx.set_materialize_grads(False)
+        if not pad_out:
+            return y, None
+        ctx.mark_non_differentiable(y)
+        return _interior(y), y
+
+    @staticmethod
+    def backward(ctx, dy, _dy_pad):
+        x_pad, w, h, mask, mean, rstd, gamma = ctx.saved_tensors
+        clients, groups, has_res, stride = ctx.meta
+        if dy is None:
+            return (None,) * 12
+        ops = load_hip_ops(required=True)
+        need_dx = ctx.needs_input_grad[0]
+        dh, dh_pad, dres, dgamma, dbeta = ops.groupnorm_bwd_pad(
+            h, mask, dy, mean, rstd, gamma, clients, groups, has_res,
+            need_dx)
+        H, W = x_pad.shape[3] - 2, x_pad.shape[4] - 2
+        dx = dw = None
+        if need_dx:
+            dx = ops.conv3x3_dgrad_p(dh_pad, w, H, W, stride)
+        if ctx.needs_input_grad[2]:
+            dw = ops.conv3x3_wgrad_p(x_pad, dh, stride)
+        return (dx, None, dw, dres if has_res else None, None,
+                dgamma.to(gamma.dtype), dbeta.to(gamma.dtype),
+                None, None, None, None, None)
+
+
+def conv3x3_gn_relu(x: torch.Tensor, x_pad, w: torch.Tensor, stride: int,
+                    clients: int, groups: int, gamma: torch.Tensor,
+                    beta: torch.Tensor, res=None, res_pad=None,
+                    pad_out: bool = True, eps: float = 1e-5):
+    """relu(gn(conv3x3(x, w, stride)) [+ res]) on [C, ch, B, H, W].
+
+    x and res may come as padded pairs (x, x_pad) / (res, res_pad) (see
+    ops/fused.py); pass None for the padded half of a dense tensor.
+    Returns a padded pair (y, y_pad); y_pad is None when the output is
+    dense — pad_out False, or a shape outside the padded path, which runs
+    today's conv (pad2d inside) followed by the dense GroupNorm."""
+    from .fused import gn_pad_shape_ok, groupnorm_act
+    if x.is_cuda and x.dtype == torch.bfloat16:
+        ops = load_hip_ops(required=True)
+        OH = (x.shape[3] + stride - 1) // stride
+        OW = (x.shape[4] + stride - 1) // stride
+        if _v6_ok(ops, x, w, stride) and gn_pad_shape_ok(w.shape[1], groups,
+                                                         OH, OW):
+            if x_pad is None:
+                x_pad = _pad(x, 1)
+            return _Conv3x3GnPadFn.apply(
+                x, x_pad, w.contiguous(), res, res_pad, gamma.contiguous(),
+                beta.contiguous(), clients, groups, eps, stride, pad_out)
+    h = client_conv3x3(x, w, stride)
+    return groupnorm_act(h, clients, groups, gamma, beta, res=res,
+                         relu=True, eps=eps), None
+
+
 def _v6_ok(ops, x: torch.Tensor, w: torch.Tensor, stride: int) -> bool:
     import os
     if os.environ.get("OLSIM_CONV_V", "") == "5":
@@ -248,15 +326,38 @@ class _Subsample2Fn(torch.autograd.Function):
         return ops.subsample2_bwd(dy.contiguous(), H, W)
 
 
-def client_conv1x1(x: torch.Tensor, w: torch.Tensor,
-                   stride: int = 1) -> torch.Tensor:
-    """1x1 conv = one batched GEMM: y[C,OC,n] = w[C,OC,IC] @ x[C,IC,n]."""
+class _Subsample2PadFn(torch.autograd.Function):
+    """_Subsample2Fn for a padded pair: reads interior pixel (2i+1, 2j+1)
+    of x_pad.  x is the graph-side view and is not read; the gradient is
+    dense, so the backward is subsample2_bwd unchanged."""
+
+    @staticmethod
+    def forward(ctx, x, x_pad):
+        ops = load_hip_ops(required=True)
+        ctx.hw = x.shape[-2:]
+        return ops.subsample2_p(x_pad)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ops = load_hip_ops(required=True)
+        H, W = ctx.hw
+        return ops.subsample2_bwd(dy.contiguous(), H, W), None
+
+
+def client_conv1x1(x: torch.Tensor, w: torch.Tensor, stride: int = 1,
+                   x_pad=None) -> torch.Tensor:
+    """1x1 conv = one batched GEMM: y[C,OC,n] = w[C,OC,IC] @ x[C,IC,n].
+    (x, x_pad) may be a padded pair (ops/fused.py); the stride-2
+    subsample then reads the padded image."""
     C, IC, B, H, W = x.shape
     OC = w.shape[1]
     if stride != 1:
         if (stride == 2 and x.is_cuda and H % 2 == 0 and W % 4 == 0
                 and x.dtype in (torch.bfloat16, torch.float32)):
-            x = _Subsample2Fn.apply(x)
+            if x_pad is not None:
+                x = _Subsample2PadFn.apply(x, x_pad)
+            else:
+                x = _Subsample2Fn.apply(x)
         else:
             x = x[:, :, :, ::stride, ::stride].contiguous()
         H, W = x.shape[-2:]

@@ -113,6 +113,21 @@ extern "C" void ols_groupnorm_bwd(const void* x, const void* y,
                                   int HW, bool relu, int layout, int dtype,
                                   hipStream_t stream);
 
+extern "C" int ols_gn_pad_ok(int ch, int G, int H, int W);
+extern "C" void ols_groupnorm_fwd_pad(
+    const void* x, const void* res, int res_mode, void* y, uint32_t* mask,
+    float* mean, float* rstd, const void* gamma, const void* beta, int B,
+    int C, int ch, int G, int H, int W, float eps, bool pad_out,
+    hipStream_t stream);
+extern "C" void ols_groupnorm_bwd_pad(
+    const void* x, const uint32_t* mask, const void* dy, void* dx,
+    void* dx_pad, void* dres, const float* mean, const float* rstd,
+    const void* gamma, float* dgamma, float* dbeta, int B, int C, int ch,
+    int G, int H, int W, hipStream_t stream);
+extern "C" void ols_subsample2p_fwd(const void* xp, void* y, int64_t planes,
+                                    int OH, int OW, int dtype,
+                                    hipStream_t stream);
+
 namespace {
 
 int dtype_code(const at::Tensor& t) {
@@ -528,6 +543,108 @@ at::Tensor subsample2_bwd(at::Tensor dy, int64_t H, int64_t W) {
   return dx;
 }
 
+// ---- padded-output GroupNorm pair (groupnorm.hip) -----------------------
+// x: [C, ch, B, H, W] bf16.  y is [C, ch, B, H+2, W+2] with a zero halo
+// (pad_out) or dense; mask is the 1-bit ReLU mask the backward consumes.
+// res: empty, dense (x's shape) or padded (y's padded shape).  ReLU is
+// always applied.
+
+bool gn_pad_ok(int64_t ch, int64_t groups, int64_t H, int64_t W) {
+  return ols_gn_pad_ok((int)ch, (int)groups, (int)H, (int)W) != 0;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> groupnorm_fwd_pad(
+    at::Tensor x, at::Tensor res, at::Tensor gamma, at::Tensor beta,
+    int64_t clients, int64_t groups, double eps, bool pad_out) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 5);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+              gamma.scalar_type() == at::kBFloat16 &&
+              beta.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(x.size(0) == clients);
+  const int64_t ch = x.size(1), B = x.size(2), H = x.size(3), W = x.size(4);
+  TORCH_CHECK(ols_gn_pad_ok((int)ch, (int)groups, (int)H, (int)W),
+              "shape unsupported by the padded GroupNorm path");
+  TORCH_CHECK(gamma.is_contiguous() && beta.is_contiguous() &&
+              gamma.numel() == clients * ch && beta.numel() == clients * ch);
+  std::vector<int64_t> psizes = {clients, ch, B, H + 2, W + 2};
+  int res_mode = 0;
+  if (res.numel() > 0) {
+    TORCH_CHECK(res.is_cuda() && res.is_contiguous() &&
+                res.scalar_type() == at::kBFloat16);
+    if (res.sizes() == x.sizes()) res_mode = 1;
+    else if (res.sizes() == at::IntArrayRef(psizes)) res_mode = 2;
+    else TORCH_CHECK(false, "groupnorm_fwd_pad: residual shape mismatch");
+  }
+  auto y = pad_out ? at::empty(psizes, x.options()) : at::empty_like(x);
+  const int64_t ngroups = B * clients * groups;
+  const int64_t n = (ch / groups) * H * W;
+  auto mask = at::empty({ngroups, (n + 31) / 32},
+                        x.options().dtype(at::kInt));
+  auto mean = at::empty({ngroups}, x.options().dtype(at::kFloat));
+  auto rstd = at::empty({ngroups}, x.options().dtype(at::kFloat));
+  ols_groupnorm_fwd_pad(
+      x.data_ptr(), res_mode ? res.data_ptr() : nullptr, res_mode,
+      y.data_ptr(), reinterpret_cast<uint32_t*>(mask.data_ptr<int>()),
+      mean.data_ptr<float>(), rstd.data_ptr<float>(), gamma.data_ptr(),
+      beta.data_ptr(), (int)B, (int)clients, (int)ch, (int)groups, (int)H,
+      (int)W, (float)eps, pad_out,
+      at::cuda::getCurrentCUDAStream().stream());
+  return {y, mask, mean, rstd};
+}
+
+// returns (dx dense, dx_pad or empty, dres dense or empty, dgamma, dbeta)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+groupnorm_bwd_pad(at::Tensor x, at::Tensor mask, at::Tensor dy,
+                  at::Tensor mean, at::Tensor rstd, at::Tensor gamma,
+                  int64_t clients, int64_t groups, bool has_res,
+                  bool want_pad) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 5);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+              dy.scalar_type() == at::kBFloat16 && dy.sizes() == x.sizes());
+  const int64_t ch = x.size(1), B = x.size(2), H = x.size(3), W = x.size(4);
+  TORCH_CHECK(x.size(0) == clients &&
+              ols_gn_pad_ok((int)ch, (int)groups, (int)H, (int)W));
+  const int64_t ngroups = B * clients * groups;
+  const int64_t n = (ch / groups) * H * W;
+  TORCH_CHECK(mask.is_contiguous() && mask.scalar_type() == at::kInt &&
+              mask.numel() == ngroups * ((n + 31) / 32));
+  TORCH_CHECK(mean.numel() == ngroups && rstd.numel() == ngroups);
+  auto dyc = dy.contiguous();
+  auto dx = at::empty_like(x);
+  auto dx_pad = want_pad ? at::empty({clients, ch, B, H + 2, W + 2},
+                                     x.options())
+                         : at::empty({0}, x.options());
+  auto dres = has_res ? at::empty_like(x) : at::empty({0}, x.options());
+  auto dgamma = at::zeros({clients, ch}, x.options().dtype(at::kFloat));
+  auto dbeta = at::zeros({clients, ch}, x.options().dtype(at::kFloat));
+  ols_groupnorm_bwd_pad(
+      x.data_ptr(), reinterpret_cast<const uint32_t*>(mask.data_ptr<int>()),
+      dyc.data_ptr(), dx.data_ptr(), want_pad ? dx_pad.data_ptr() : nullptr,
+      has_res ? dres.data_ptr() : nullptr, mean.data_ptr<float>(),
+      rstd.data_ptr<float>(), gamma.data_ptr(), dgamma.data_ptr<float>(),
+      dbeta.data_ptr<float>(), (int)B, (int)clients, (int)ch, (int)groups,
+      (int)H, (int)W, at::cuda::getCurrentCUDAStream().stream());
+  return {dx, dx_pad, dres, dgamma, dbeta};
+}
+
+// padded-input subsample: xp [.., H+2, W+2] -> [.., H/2, W/2]
+at::Tensor subsample2_p(at::Tensor xp) {
+  TORCH_CHECK(xp.is_cuda() && xp.is_contiguous() && xp.dim() >= 2);
+  int H = xp.size(-2) - 2, W = xp.size(-1) - 2;
+  TORCH_CHECK(H >= 2 && H % 2 == 0 && W % 4 == 0);
+  TORCH_CHECK(xp.scalar_type() == at::kBFloat16 ||
+              xp.scalar_type() == at::kFloat);
+  int64_t planes = xp.numel() / ((int64_t)(H + 2) * (W + 2));
+  auto sizes = xp.sizes().vec();
+  sizes[sizes.size() - 2] = H / 2;
+  sizes[sizes.size() - 1] = W / 2;
+  auto y = at::empty(sizes, xp.options());
+  int dt = xp.scalar_type() == at::kBFloat16 ? 1 : 0;
+  ols_subsample2p_fwd(xp.data_ptr(), y.data_ptr(), planes, H / 2, W / 2, dt,
+                      at::cuda::getCurrentCUDAStream().stream());
+  return y;
+}
+
 // ---- client replica broadcast (replicate.hip) ---------------------------
 
 at::Tensor replicate(at::Tensor src, int64_t clients) {
@@ -641,6 +758,14 @@ TORCH_LIBRARY(olsim_hip, m) {
   m.def("replicate(Tensor src, int clients) -> Tensor");
   m.def("subsample2(Tensor x) -> Tensor");
   m.def("subsample2_bwd(Tensor dy, int H, int W) -> Tensor");
+  m.def("subsample2_p(Tensor xp) -> Tensor");
+  m.def("gn_pad_ok(int ch, int groups, int H, int W) -> bool", &gn_pad_ok);
+  m.def("groupnorm_fwd_pad(Tensor x, Tensor res, Tensor gamma, Tensor beta, "
+        "int clients, int groups, float eps, bool pad_out) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
+  m.def("groupnorm_bwd_pad(Tensor x, Tensor mask, Tensor dy, Tensor mean, "
+        "Tensor rstd, Tensor gamma, int clients, int groups, bool has_res, "
+        "bool want_pad) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("synth_batch(Tensor x, Tensor y, float s, float t) -> Tensor");
   m.def("layernorm_fwd(Tensor x, Tensor gamma, Tensor beta, float eps) -> (Tensor, Tensor, Tensor)");
   m.def("layernorm_bwd(Tensor x, Tensor dy, Tensor gamma, Tensor mean, Tensor rstd) -> (Tensor, Tensor, Tensor)");
@@ -670,6 +795,9 @@ TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("replicate", &replicate);
   m.impl("subsample2", &subsample2);
   m.impl("subsample2_bwd", &subsample2_bwd);
+  m.impl("subsample2_p", &subsample2_p);
+  m.impl("groupnorm_fwd_pad", &groupnorm_fwd_pad);
+  m.impl("groupnorm_bwd_pad", &groupnorm_bwd_pad);
   m.impl("synth_batch", &synth_batch);
   m.impl("layernorm_fwd", &layernorm_fwd);
   m.impl("layernorm_bwd", &layernorm_bwd);

@@ -117,6 +117,30 @@ __global__ __launch_bounds__(OLS_THREADS) void k_subsample2_fwd(
   }
 }
 
+// Padded-input variant: x carries a 1-element halo ([.., 2*OH+2, 2*OW+2],
+// the layout the padded-output GroupNorm writes), so output (oi, oj) is
+// interior pixel (2*oi+1, 2*oj+1).  The backward is k_subsample2_bwd
+// unchanged: gradients stay dense.
+template <typename T>
+__global__ __launch_bounds__(OLS_THREADS) void k_subsample2p_fwd(
+    const T* __restrict__ xp, T* __restrict__ y, int64_t n_out2, int OH,
+    int OW) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int PW = OW * 2 + 2, PH = OH * 2 + 2, OW2 = OW / 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n_out2; i += stride) {
+    const int64_t plane = i / (OH * OW2);
+    const int rem = (int)(i - plane * (OH * OW2));
+    const int oi = rem / OW2, oj2 = (rem - (rem / OW2) * OW2) * 2;
+    const T* p = xp + (plane * PH + 2 * oi + 1) * (int64_t)PW + 2 * oj2 + 1;
+    Pack<T, 2> o;
+    o.v[0] = p[0];
+    o.v[1] = p[2];
+    *reinterpret_cast<Pack<T, 2>*>(
+        &y[(plane * OH + oi) * (int64_t)OW + oj2]) = o;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(OLS_THREADS) void k_subsample2_bwd(
     const T* __restrict__ dy, T* __restrict__ dx, int64_t n_in2, int H,
@@ -150,6 +174,20 @@ extern "C" void ols_subsample2_fwd(const void* x, void* y, int64_t planes,
   else
     hipLaunchKernelGGL((k_subsample2_fwd<float>), grid, block, 0, stream,
                        (const float*)x, (float*)y, n2, OH, OW);
+}
+
+extern "C" void ols_subsample2p_fwd(const void* xp, void* y, int64_t planes,
+                                    int OH, int OW, int dtype,
+                                    hipStream_t stream) {
+  const int64_t n2 = planes * OH * (OW / 2);
+  dim3 grid(ols_grid(n2, OLS_THREADS)), block(OLS_THREADS);
+  if (dtype == 1)
+    hipLaunchKernelGGL((k_subsample2p_fwd<__hip_bfloat16>), grid, block, 0,
+                       stream, (const __hip_bfloat16*)xp, (__hip_bfloat16*)y,
+                       n2, OH, OW);
+  else
+    hipLaunchKernelGGL((k_subsample2p_fwd<float>), grid, block, 0, stream,
+                       (const float*)xp, (float*)y, n2, OH, OW);
 }
 
 extern "C" void ols_subsample2_bwd(const void* dy, void* dx, int64_t planes,

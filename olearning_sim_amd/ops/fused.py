@@ -288,6 +288,89 @@ def groupnorm_act(x: torch.Tensor, clients: int, groups: int,
     return torch.nn.functional.relu(y) if relu else y
 
 
+# -- padded-output GroupNorm (feeds the v6 padded 3x3 conv family) ----------
+#
+# A "padded pair" is (y, y_pad): y_pad is the activation [C, ch, B, H+2,
+# W+2] with a 1-element zero halo that the kernels read; y is its interior
+# view y_pad[..., 1:-1, 1:-1] and exists for the autograd graph only —
+# gradients flow through it dense and unpadded, no kernel reads it.
+
+def gn_pad_shape_ok(ch: int, groups: int, H: int, W: int) -> bool:
+    """True when both LDS-staged directions of the padded pair fit a
+    [*, ch, *, H, W] bf16 GPU activation and OLSIM_GN_PAD=0 (the A/B
+    switch back to dense GN + pad2d) is not set."""
+    if os.environ.get("OLSIM_GN_PAD", "1") == "0":
+        return False
+    ops = load_hip_ops(required=True)
+    return bool(ops.gn_pad_ok(ch, groups, H, W))
+
+
+def gn_pad_eligible(x: torch.Tensor, groups: int) -> bool:
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 5):
+        return False
+    return gn_pad_shape_ok(x.shape[1], groups, x.shape[3], x.shape[4])
+
+
+def _res_arg(x, res, res_pad):
+    """Residual tensor handed to groupnorm_fwd_pad: the padded image when
+    the residual is a padded pair, the dense tensor otherwise."""
+    if res is None:
+        return torch.empty(0, dtype=x.dtype, device=x.device)
+    return res_pad if res_pad is not None else res.contiguous()
+
+
+def _interior(y_pad: torch.Tensor) -> torch.Tensor:
+    return y_pad[..., 1:-1, 1:-1]
+
+
+class _GroupNormPadFn(torch.autograd.Function):
+    """relu(gn(x) [+ res]) written as a padded pair.  Saves x and a 1-bit
+    ReLU mask (not y) for the backward."""
+
+    @staticmethod
+    def forward(ctx, x, res, res_pad, gamma, beta, clients, groups, eps):
+        ops = load_hip_ops(required=True)
+        y_pad, mask, mean, rstd = ops.groupnorm_fwd_pad(
+            x, _res_arg(x, res, res_pad), gamma, beta, clients, groups, eps,
+            True)
+        ctx.save_for_backward(x, mask, mean, rstd, gamma)
+        ctx.meta = (clients, groups, res is not None)
+        ctx.mark_non_differentiable(y_pad)
+        # y_pad never has a gradient; do not let autograd zero-fill one
+        ctx.set_materialize_grads(False)
+        return _interior(y_pad), y_pad
+
+    @staticmethod
+    def backward(ctx, dy, _dy_pad):
+        x, mask, mean, rstd, gamma = ctx.saved_tensors
+        clients, groups, has_res = ctx.meta
+        if dy is None:
+            return (None,) * 8
+        ops = load_hip_ops(required=True)
+        dx, _, dres, dgamma, dbeta = ops.groupnorm_bwd_pad(
+            x, mask, dy, mean, rstd, gamma, clients, groups, has_res, False)
+        return (dx, dres if has_res else None, None,
+                dgamma.to(gamma.dtype), dbeta.to(gamma.dtype),
+                None, None, None)
+
+
+def groupnorm_relu_pad(x: torch.Tensor, clients: int, groups: int,
+                       gamma: torch.Tensor, beta: torch.Tensor,
+                       res: Optional[torch.Tensor] = None,
+                       res_pad: Optional[torch.Tensor] = None,
+                       eps: float = 1e-5):
+    """relu(gn(x)*gamma + beta [+ res]) for x [C, ch, B, H, W] as a padded
+    pair (y, y_pad).  res may itself be a padded pair (res, res_pad).
+    Ineligible shapes take the dense kernels and return (y, None); the
+    consuming conv then pads its input itself."""
+    if gn_pad_eligible(x, groups):
+        return _GroupNormPadFn.apply(x.contiguous(), res, res_pad,
+                                     gamma.contiguous(), beta.contiguous(),
+                                     clients, groups, eps)
+    return groupnorm_act(x, clients, groups, gamma, beta, res=res,
+                         relu=True, eps=eps), None
+
+
 def fast_transpose(x: torch.Tensor) -> torch.Tensor:
     """[B, M, N] -> contiguous [B, N, M] via the LDS-tiled transpose
     kernel (torch's transpose+contiguous runs the generic strided copy
