@@ -886,8 +886,11 @@ extern "C" void ols_conv3x3_dgrad(const void* dy, const void* w, void* dx,
       g.pow2 = 1;
     }
   }
+  // dgrad_v5 decomposes n with log2(W) = log2(OW * stride) and H == W:
+  // an odd plane at stride 2 (OH = ceil(H/2)) takes the generic kernel
   const bool v5_ok = g.pow2 && ((OC * 9) % CV2_BK == 0)
-                     && (stride == 1 || stride == 2) && H == W;
+                     && (stride == 1 || stride == 2) && H == W
+                     && H == g.OH * stride;
   if (v5_ok) {
     dim3 grid5(ceil_div(B * H * W, CV2_BN), ceil_div(IC, CV2_BM), C);
     if (stride == 1)

@@ -1350,6 +1350,9 @@ extern "C" int ols_conv3x3_v6_ok(int IC, int OC, int B, int H, int W,
   auto p2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
   int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
   if (!p2(OH) || !p2(OW) || OW < 4) return 0;
+  // stride-2 dgrad scatters into a 2*OH x 2*OW dX plane: odd H or W
+  // (7 -> 4) would index dy_pad and dx with the wrong plane sizes
+  if (stride == 2 && ((H | W) & 1)) return 0;
   if ((IC * 9) % CV6_BK != 0) return 0;             // fwd K
   if ((OC * 9) % CV6_BK != 0) return 0;             // dgrad K (s=1)
   if (stride == 2 && OC % CV6_BK != 0) return 0;    // smallest s2 class K=OC

@@ -255,12 +255,14 @@ __global__ __launch_bounds__(OLS_THREADS) void k_gn_bwd(
   // and the per-channel dgamma/dbeta partials are reduced across the
   // lanes that share a channel BEFORE one LDS atomic — the previous
   // per-element atomics serialised up to 256 ways on one address when
-  // HW >= the block span.  lpc = lanes per channel (pow2).
+  // HW >= the block span.  lpc = lanes per channel: the largest power of
+  // two dividing hv, so an aligned group of lpc lanes never straddles a
+  // channel (hv itself is not a power of two for e.g. 28x28 or 4x6 planes).
   const bool vec = (HW % 8) == 0;
   if (vec) {
     const int nv = n / 8;
     const int hv = HW / 8;                     // vectors per channel-plane
-    const int lpc = min(WAVE, hv);             // pow2 (HW, 8 are pow2)
+    const int lpc = min(WAVE, hv & -hv);
     // whole waves iterate together (the shuffle reduce needs every lane
     // of a channel group present; groups of lpc consecutive vectors are
     // always fully active or fully inactive since lpc divides nv)
@@ -420,7 +422,7 @@ __global__ __launch_bounds__(OLS_THREADS) void k_gn_bwd_lds(
   float s1 = 0.f, s2 = 0.f;
   const int nv = n / 8;
   const int hv = HW / 8;
-  const int lpc = min(WAVE, hv);
+  const int lpc = min(WAVE, hv & -hv);   // pow2 divisor of hv (see k_gn_bwd)
   for (int v8 = threadIdx.x; v8 - lane < nv; v8 += blockDim.x) {
     const bool active = v8 < nv;
     int i = active ? v8 * 8 : 0;
@@ -713,7 +715,7 @@ __global__ __launch_bounds__(OLS_THREADS) void k_gn_bwd_pad(
   float s1 = 0.f, s2 = 0.f;
   const int nv = n / 8;
   const int hv = HW / 8;
-  const int lpc = min(WAVE, hv);
+  const int lpc = min(WAVE, hv & -hv);   // pow2 divisor of hv (see k_gn_bwd)
   for (int v8 = threadIdx.x; v8 - lane < nv; v8 += blockDim.x) {
     const bool active = v8 < nv;
     int i = active ? v8 * 8 : 0;

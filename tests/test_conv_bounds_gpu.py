@@ -1,0 +1,189 @@
+"""conv3x3 (every kernel family and dispatch branch), conv5x5 and the
+2x2 max-pool against fp64 references with the derived bounds of
+tests/kernel_bounds.py.  Each conv3x3 case asserts the family the
+dispatcher takes, so a silent change of route fails here."""
+
+import pytest
+import torch
+
+import kernel_bounds as kb
+from kernel_bounds import assert_bounded, upcast
+
+pytestmark = pytest.mark.gpu
+
+BF = torch.bfloat16
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _require_ext():
+    from olearning_sim_amd.ops import load_hip_ops
+    load_hip_ops(required=True)
+
+
+_REF_CACHE: dict = {}
+
+
+def _conv3_case(shape):
+    """Inputs and fp64 reference for (C, IC, OC, B, H, W, stride);
+    computed once and shared between the tests that use the shape."""
+    if shape not in _REF_CACHE:
+        C, IC, OC, B, H, W, s = shape
+        g = torch.Generator().manual_seed(hash(shape) % (2 ** 31))
+        OH, OW = (H + s - 1) // s, (W + s - 1) // s
+        x = (torch.randn(C, IC, B, H, W, generator=g) * 0.5).to(BF)
+        w = (torch.randn(C, OC, IC, 3, 3, generator=g) * 0.1).to(BF)
+        dy = (torch.randn(C, OC, B, OH, OW, generator=g) * 0.1).to(BF)
+        ref = kb.conv_ref(upcast(x), upcast(w), upcast(dy), s, 1)
+        _REF_CACHE[shape] = (x, w, dy, ref)
+    return _REF_CACHE[shape]
+
+
+def _check_conv3x3(shape, v6, tag):
+    from olearning_sim_amd.ops.conv import client_conv3x3
+    from olearning_sim_amd.ops.fused import load_hip_ops
+    ops = load_hip_ops(required=True)
+    C, IC, OC, B, H, W, s = shape
+    assert bool(ops.conv3x3_v6_ok(IC, OC, B, H, W, s)) == v6, \
+        f"{shape}: expected the {'v6' if v6 else 'v5'} family"
+    x, w, dy, ref = _conv3_case(shape)
+    xg = x.cuda().requires_grad_(True)
+    wg = w.cuda().requires_grad_(True)
+    y = client_conv3x3(xg, wg, s)
+    y.backward(dy.cuda())
+    OH, OW = y.shape[-2:]
+    assert_bounded(y, ref["y"], ref["y_scale"], IC * 9, BF,
+                   label=tag + ".fwd")
+    assert_bounded(xg.grad, ref["dx"], ref["dx_scale"], OC * 9, BF,
+                   label=tag + ".dgrad")
+    assert_bounded(wg.grad, ref["dw"], ref["dw_scale"], B * OH * OW, BF,
+                   label=tag + ".wgrad")
+
+
+# (C, IC, OC, B, H, W, stride) -> takes the v6 padded family?
+V6_SHAPES = [
+    (1, 64, 64, 1, 32, 32, 1),     # fwd_v7<5>: the benchmark's stage 0
+    (2, 64, 64, 2, 8, 16, 1),      # non-square planes
+    (2, 64, 64, 2, 16, 8, 1),
+    (2, 64, 64, 2, 4, 32, 1),
+    (2, 64, 128, 2, 16, 32, 2),    # stride-2 parity classes, 8x16 dy plane
+    (2, 64, 96, 2, 4, 4, 1),       # OC tile tail; B*OH*OW = 32 < one N tile
+    (2, 32, 32, 2, 4, 4, 1),       # half M tile, K = 288
+    (2, 64, 64, 4, 4, 4, 1),       # OW = 4, B*OH*OW = 64 (wgrad_v7 under DW64)
+    (2, 64, 128, 4, 8, 8, 2),      # stride 2 at OW = 4
+]
+V5_SHAPES = [
+    (2, 64, 64, 4, 8, 4, 2),       # OW = 2 < 4: below the v6 floor
+    (2, 8, 24, 3, 6, 10, 1),       # generic kernels: no pow2 plane
+    (2, 16, 16, 2, 8, 16, 1),      # fwd_v2 (K % 32 != 0) + wgrad_v5
+    (1, 3, 8, 2, 7, 9, 2),         # odd, non-pow2, stride 2
+    # odd planes at stride 2 (7 -> 4): v6 and dgrad_v5 assume H = 2*OH
+    (2, 64, 64, 2, 7, 7, 2),
+    (2, 64, 64, 2, 7, 8, 2),
+]
+
+
+@pytest.mark.parametrize("shape", V6_SHAPES, ids=str)
+def test_conv3x3_v6_family_bounded(shape, monkeypatch):
+    for var in ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
+                "OLSIM_CONV_DW8"):
+        monkeypatch.delenv(var, raising=False)
+    _check_conv3x3(shape, True, "conv3.v6")
+
+
+@pytest.mark.parametrize("shape", V5_SHAPES, ids=str)
+def test_conv3x3_v5_family_bounded(shape, monkeypatch):
+    for var in ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
+                "OLSIM_CONV_DW8"):
+        monkeypatch.delenv(var, raising=False)
+    _check_conv3x3(shape, False, "conv3.v5")
+
+
+@pytest.mark.parametrize("var", ["OLSIM_CONV_V8", "OLSIM_CONV_DW64"])
+@pytest.mark.parametrize("shape", V6_SHAPES, ids=str)
+def test_conv3x3_env_gated_kernels_bounded(shape, var, monkeypatch):
+    """fwd_v8 (OLSIM_CONV_V8) and dgrad_v7 / wgrad_v7 (OLSIM_CONV_DW64);
+    the launchers read the environment on every call."""
+    for other in ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
+                  "OLSIM_CONV_DW8"):
+        monkeypatch.delenv(other, raising=False)
+    monkeypatch.setenv(var, "1")
+    _check_conv3x3(shape, True, "conv3." + var.rsplit("_", 1)[1].lower())
+
+
+# ---------------------------------------------------------------------------
+# conv5x5
+
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("shape", [(2, 4, 8, 2, 12, 20), (2, 16, 16, 2, 12, 12)],
+                         ids=str)
+def test_conv5x5_bounded(shape, relu):
+    """Non-square plane and the IC = OC = 16 limit.  ReLU: signs the
+    fp64 pre-activation cannot decide follow the kernel's own mask."""
+    from olearning_sim_amd.ops.conv import client_conv5x5, conv5x5_supported
+    C, IC, OC, B, H, W = shape
+    g = torch.Generator().manual_seed(11)
+    x = (torch.randn(C, IC, B, H, W, generator=g) * 0.5).to(BF)
+    w = (torch.randn(C, OC, IC, 5, 5, generator=g) * 0.1).to(BF)
+    b = (torch.randn(C, OC, generator=g) * 0.1).to(BF)
+    dy = (torch.randn(C, OC, B, H - 4, W - 4, generator=g) * 0.1).to(BF)
+
+    xg = x.cuda().requires_grad_(True)
+    wg = w.cuda().requires_grad_(True)
+    bg = b.cuda().requires_grad_(True)
+    assert conv5x5_supported(xg, wg)
+    y = client_conv5x5(xg, wg, bg, relu=relu)
+    y.backward(dy.cuda())
+
+    n = IC * 25 + 1
+    x64, w64, b64, dy64 = upcast(x), upcast(w), upcast(b), upcast(dy)
+    pre = kb.conv_math(x64, w64, 1, 0, b64)
+    pre_scale = kb.conv_math(x64.abs(), w64.abs(), 1, 0, b64.abs())
+    want = pre
+    if relu:
+        dec = kb.relu_decided(pre, pre_scale, n, BF, label="conv5")
+        dy64 = dy64 * kb.relu_mask(pre, dec, y).to(dy64.dtype)
+        want = pre.clamp_min(0)
+    assert_bounded(y, want, pre_scale, n, BF, label="conv5.fwd")
+    ref = kb.conv_ref(x64, w64, dy64, 1, 0)
+    nq = B * (H - 4) * (W - 4)
+    assert_bounded(xg.grad, ref["dx"], ref["dx_scale"], OC * 25, BF,
+                   label="conv5.dgrad")
+    assert_bounded(wg.grad, ref["dw"], ref["dw_scale"], nq, BF,
+                   label="conv5.wgrad")
+    assert_bounded(bg.grad, dy64.sum(dim=(2, 3, 4)),
+                   dy64.abs().sum(dim=(2, 3, 4)), nq, BF, label="conv5.dbias")
+
+
+# ---------------------------------------------------------------------------
+# pool2x2
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("shape", [(3, 4, 6, 10), (2, 3, 2, 8, 8)], ids=str)
+def test_pool2x2_gradient_is_one_hot_per_window(shape, dtype):
+    """Tie-proof and exact: y is the window maximum, and in every 2x2
+    window the gradient is dy at exactly one position whose x equals the
+    maximum and zero at the other three.  bf16 randn inputs contain real
+    ties, so the argmax order is not assumed."""
+    from olearning_sim_amd.ops.conv import max_pool2x2
+    g = torch.Generator().manual_seed(21)
+    x = torch.randn(*shape, generator=g).to(dtype)
+    x[..., 0:2, 0:2] = 0.5                  # a window of four equal values
+    H, W = shape[-2:]
+    dy = torch.randn(*shape[:-2], H // 2, W // 2, generator=g).to(dtype)
+    dy[dy == 0] = 1.0                       # a zero dy could not be located
+    xg = x.cuda().requires_grad_(True)
+    y = max_pool2x2(xg)
+    y.backward(dy.cuda())
+
+    def windows(t):                         # [..., OH, OW, 4]
+        t = t.reshape(*t.shape[:-2], H // 2, 2, W // 2, 2)
+        return t.transpose(-3, -2).reshape(*t.shape[:-4], H // 2, W // 2, 4)
+
+    xw, gw = windows(x), windows(xg.grad.cpu())
+    wmax = xw.max(dim=-1).values
+    assert torch.equal(y.detach().cpu(), wmax)
+    hit = gw != 0
+    assert bool((hit.sum(-1) == 1).all()), "not exactly one routed position"
+    assert torch.equal(gw.sum(-1), dy), "routed value is not dy"
+    assert torch.equal(xw[hit], wmax.reshape(-1)), \
+        "gradient routed to a non-maximal position"
