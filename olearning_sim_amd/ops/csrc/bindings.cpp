@@ -6,6 +6,8 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 
+#include "groupnorm.h"
+
 extern "C" void ols_fused_sgd_update_flat(
     void* buf, const void* grad, const void* master, const int64_t* offs,
     int nblocks, int64_t clients, int64_t total, float lr, float mu,
@@ -200,36 +202,54 @@ int gn_dtype(const at::Tensor& t) {
   return t.scalar_type() == at::kFloat ? 0 : 1;
 }
 
+// Shape of a GroupNorm input, for all four wrappers.  4-D x is
+// [B, C*ch, H, W] (layout 0), 5-D x is [C, ch, B, H, W] (layout 1);
+// ngroups = B*C*G workgroups of n = (ch/G)*H*W elements each.
+struct GnDims {
+  int layout;
+  int64_t B, ch, H, W, HW, ngroups, n;
+};
+
+GnDims gn_dims(const at::Tensor& x, int64_t clients, int64_t groups) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
+                  (x.dim() == 4 || x.dim() == 5),
+              "groupnorm: x must be a contiguous 4-D or 5-D device tensor");
+  TORCH_CHECK(clients > 0 && groups > 0);
+  GnDims d;
+  d.layout = x.dim() == 4 ? 0 : 1;
+  if (d.layout == 0) {
+    TORCH_CHECK(x.size(1) % clients == 0);
+    d.B = x.size(0); d.ch = x.size(1) / clients;
+  } else {
+    TORCH_CHECK(x.size(0) == clients);
+    d.ch = x.size(1); d.B = x.size(2);
+  }
+  d.H = x.size(-2); d.W = x.size(-1); d.HW = d.H * d.W;
+  TORCH_CHECK(d.ch % groups == 0);
+  TORCH_CHECK(d.ch / groups <= MAX_CG, "groupnorm: ch/G > ", MAX_CG,
+              " unsupported");
+  d.ngroups = d.B * clients * groups;
+  d.n = (d.ch / groups) * d.HW;
+  return d;
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor> groupnorm_fwd(
     at::Tensor x, at::Tensor res, at::Tensor gamma, at::Tensor beta,
     int64_t clients, int64_t groups, double eps, bool relu) {
-  // dim 4: [B, C*ch, H, W] (layout 0); dim 5: [C, ch, B, H, W] (layout 1)
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
-              (x.dim() == 4 || x.dim() == 5));
-  const int layout = x.dim() == 4 ? 0 : 1;
-  int64_t B, ch, HW;
-  if (layout == 0) {
-    B = x.size(0); ch = x.size(1) / clients; HW = x.size(2) * x.size(3);
-    TORCH_CHECK(x.size(1) % clients == 0);
-  } else {
-    TORCH_CHECK(x.size(0) == clients);
-    ch = x.size(1); B = x.size(2); HW = x.size(3) * x.size(4);
-  }
-  TORCH_CHECK(ch % groups == 0);
-  TORCH_CHECK(ch / groups <= 128, "groupnorm: ch/G > 128 unsupported");
+  const GnDims d = gn_dims(x, clients, groups);
   TORCH_CHECK(gamma.is_contiguous() && beta.is_contiguous());
   const bool has_res = res.numel() > 0;
   if (has_res) TORCH_CHECK(res.is_contiguous() && res.sizes() == x.sizes());
   auto y = at::empty_like(x);
-  const int64_t ngroups = B * clients * groups;
-  auto mean = at::empty({ngroups}, x.options().dtype(at::kFloat));
-  auto rstd = at::empty({ngroups}, x.options().dtype(at::kFloat));
+  auto mean = at::empty({d.ngroups}, x.options().dtype(at::kFloat));
+  auto rstd = at::empty({d.ngroups}, x.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
   ols_groupnorm_fwd(x.data_ptr(), has_res ? res.data_ptr() : nullptr,
                     y.data_ptr(), mean.data_ptr<float>(),
                     rstd.data_ptr<float>(), gamma.data_ptr(), beta.data_ptr(),
-                    (int)B, (int)clients, (int)ch, (int)groups, (int)HW,
-                    (float)eps, relu, layout, gn_dtype(x), stream.stream());
+                    (int)d.B, (int)clients, (int)d.ch, (int)groups,
+                    (int)d.HW, (float)eps, relu, d.layout, gn_dtype(x),
+                    stream.stream());
   return {y, mean, rstd};
 }
 
@@ -237,28 +257,26 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> groupnorm_bwd(
     at::Tensor x, at::Tensor y, at::Tensor dy, at::Tensor mean,
     at::Tensor rstd, at::Tensor gamma, int64_t clients, int64_t groups,
     bool has_res, bool relu) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && y.is_contiguous());
+  const GnDims d = gn_dims(x, clients, groups);
+  TORCH_CHECK(y.is_contiguous() && y.sizes() == x.sizes() &&
+              y.scalar_type() == x.scalar_type());
+  TORCH_CHECK(dy.sizes() == x.sizes() &&
+              dy.scalar_type() == x.scalar_type());
+  TORCH_CHECK(mean.numel() == d.ngroups && rstd.numel() == d.ngroups);
   auto dyc = dy.contiguous();
-  const int layout = x.dim() == 4 ? 0 : 1;
-  int64_t B, ch, HW;
-  if (layout == 0) {
-    B = x.size(0); ch = x.size(1) / clients; HW = x.size(2) * x.size(3);
-  } else {
-    ch = x.size(1); B = x.size(2); HW = x.size(3) * x.size(4);
-  }
   auto dx = at::empty_like(x);
   auto dres = has_res ? at::empty_like(x)
                       : at::empty({0}, x.options());
-  auto dgamma = at::zeros({clients, ch}, x.options().dtype(at::kFloat));
-  auto dbeta = at::zeros({clients, ch}, x.options().dtype(at::kFloat));
+  auto dgamma = at::zeros({clients, d.ch}, x.options().dtype(at::kFloat));
+  auto dbeta = at::zeros({clients, d.ch}, x.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
   ols_groupnorm_bwd(x.data_ptr(), y.data_ptr(), dyc.data_ptr(),
                     dx.data_ptr(), has_res ? dres.data_ptr() : nullptr,
                     mean.data_ptr<float>(), rstd.data_ptr<float>(),
                     gamma.data_ptr(), dgamma.data_ptr<float>(),
-                    dbeta.data_ptr<float>(), (int)B, (int)clients, (int)ch,
-                    (int)groups, (int)HW, relu, layout, gn_dtype(x),
-                    stream.stream());
+                    dbeta.data_ptr<float>(), (int)d.B, (int)clients,
+                    (int)d.ch, (int)groups, (int)d.HW, relu, d.layout,
+                    gn_dtype(x), stream.stream());
   return {dx, dres, dgamma, dbeta};
 }
 
@@ -556,12 +574,12 @@ bool gn_pad_ok(int64_t ch, int64_t groups, int64_t H, int64_t W) {
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> groupnorm_fwd_pad(
     at::Tensor x, at::Tensor res, at::Tensor gamma, at::Tensor beta,
     int64_t clients, int64_t groups, double eps, bool pad_out) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 5);
+  TORCH_CHECK(x.dim() == 5);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
               gamma.scalar_type() == at::kBFloat16 &&
               beta.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(x.size(0) == clients);
-  const int64_t ch = x.size(1), B = x.size(2), H = x.size(3), W = x.size(4);
+  const GnDims d = gn_dims(x, clients, groups);
+  const int64_t ch = d.ch, B = d.B, H = d.H, W = d.W;
   TORCH_CHECK(ols_gn_pad_ok((int)ch, (int)groups, (int)H, (int)W),
               "shape unsupported by the padded GroupNorm path");
   TORCH_CHECK(gamma.is_contiguous() && beta.is_contiguous() &&
@@ -576,12 +594,10 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> groupnorm_fwd_pad(
     else TORCH_CHECK(false, "groupnorm_fwd_pad: residual shape mismatch");
   }
   auto y = pad_out ? at::empty(psizes, x.options()) : at::empty_like(x);
-  const int64_t ngroups = B * clients * groups;
-  const int64_t n = (ch / groups) * H * W;
-  auto mask = at::empty({ngroups, (n + 31) / 32},
+  auto mask = at::empty({d.ngroups, (d.n + 31) / 32},
                         x.options().dtype(at::kInt));
-  auto mean = at::empty({ngroups}, x.options().dtype(at::kFloat));
-  auto rstd = at::empty({ngroups}, x.options().dtype(at::kFloat));
+  auto mean = at::empty({d.ngroups}, x.options().dtype(at::kFloat));
+  auto rstd = at::empty({d.ngroups}, x.options().dtype(at::kFloat));
   ols_groupnorm_fwd_pad(
       x.data_ptr(), res_mode ? res.data_ptr() : nullptr, res_mode,
       y.data_ptr(), reinterpret_cast<uint32_t*>(mask.data_ptr<int>()),
@@ -598,17 +614,15 @@ groupnorm_bwd_pad(at::Tensor x, at::Tensor mask, at::Tensor dy,
                   at::Tensor mean, at::Tensor rstd, at::Tensor gamma,
                   int64_t clients, int64_t groups, bool has_res,
                   bool want_pad) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 5);
+  TORCH_CHECK(x.dim() == 5);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
               dy.scalar_type() == at::kBFloat16 && dy.sizes() == x.sizes());
-  const int64_t ch = x.size(1), B = x.size(2), H = x.size(3), W = x.size(4);
-  TORCH_CHECK(x.size(0) == clients &&
-              ols_gn_pad_ok((int)ch, (int)groups, (int)H, (int)W));
-  const int64_t ngroups = B * clients * groups;
-  const int64_t n = (ch / groups) * H * W;
+  const GnDims d = gn_dims(x, clients, groups);
+  const int64_t ch = d.ch, B = d.B, H = d.H, W = d.W;
+  TORCH_CHECK(ols_gn_pad_ok((int)ch, (int)groups, (int)H, (int)W));
   TORCH_CHECK(mask.is_contiguous() && mask.scalar_type() == at::kInt &&
-              mask.numel() == ngroups * ((n + 31) / 32));
-  TORCH_CHECK(mean.numel() == ngroups && rstd.numel() == ngroups);
+              mask.numel() == d.ngroups * ((d.n + 31) / 32));
+  TORCH_CHECK(mean.numel() == d.ngroups && rstd.numel() == d.ngroups);
   auto dyc = dy.contiguous();
   auto dx = at::empty_like(x);
   auto dx_pad = want_pad ? at::empty({clients, ch, B, H + 2, W + 2},

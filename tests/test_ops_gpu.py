@@ -185,6 +185,25 @@ def test_groupnorm_fused_matches_reference(shape, relu, res):
         torch.testing.assert_close(rf.grad.float(), rr.grad, atol=1e-1, rtol=1e-1)
 
 
+def test_groupnorm_rejects_oversized_group_both_directions():
+    """ch/G = 129 is past MAX_CG, the length of the backward's per-channel
+    LDS arrays: both wrappers must raise before any kernel is launched."""
+    from olearning_sim_amd.ops import load_hip_ops
+    ops = load_hip_ops(required=True)
+    C, ch, B, H, W, G = 1, 1032, 1, 2, 2, 8
+    x = torch.zeros(C, ch, B, H, W, dtype=torch.bfloat16, device="cuda")
+    gamma = torch.ones(C, ch, dtype=torch.bfloat16, device="cuda")
+    beta = torch.zeros(C, ch, dtype=torch.bfloat16, device="cuda")
+    empty = torch.empty(0, dtype=torch.bfloat16, device="cuda")
+    with pytest.raises(RuntimeError, match="ch/G"):
+        ops.groupnorm_fwd(x, empty, gamma, beta, C, G, 1e-5, False)
+    stats = torch.zeros(B * C * G, device="cuda")
+    with pytest.raises(RuntimeError, match="ch/G"):
+        ops.groupnorm_bwd(x, x.clone(), x.clone(), stats, stats.clone(),
+                          gamma, C, G, False, False)
+    torch.cuda.synchronize()
+
+
 def test_engine_per_tier_accounting_gpu():
     """Per-(data x tier) segment accounting with GPU behaviour sampling:
     vectors partition the cohort and feed the result rows."""
