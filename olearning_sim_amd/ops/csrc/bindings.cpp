@@ -60,6 +60,7 @@ extern "C" void ols_conv5x5_fwd(const void* x, const void* w, const void* b,
 extern "C" void ols_conv5x5_dgrad(const void* dyp, const void* w, void* dx,
                                   const int* ntab, int C, int IC, int OC,
                                   int B, int H, int W, hipStream_t stream);
+extern "C" int ols_conv5x5_route(int dir, int IC, int OC, int H, int W);
 extern "C" void ols_conv5x5_wgrad(const void* x, const void* dy, void* dw,
                                   float* part, const int* ntab, int C,
                                   int IC, int OC, int B, int H, int W,
@@ -376,6 +377,18 @@ at::Tensor conv3x3_dgrad_p(at::Tensor dyp, at::Tensor w, int64_t H, int64_t W,
 // ---- 5x5 VALID family (client_conv5.hip, LeNet) -------------------------
 // ntab: int32 [B*OH*OW] plane offsets (b*H*W + oh*W + ow) built host-side
 
+// Which kernel a [*, IC, *, H, W] x and OC output channels run in
+// direction dir ("fwd", "dgrad", "wgrad"): "direct", "mfma" or
+// "two_stage".  Same host functions the launchers branch on; reads
+// OLSIM_CONV5 on every call.
+std::string conv5x5_route(std::string dir, int64_t IC, int64_t OC, int64_t H,
+                          int64_t W) {
+  int d = dir == "fwd" ? 0 : dir == "dgrad" ? 1 : dir == "wgrad" ? 2 : -1;
+  TORCH_CHECK(d >= 0, "conv5x5_route: dir must be fwd, dgrad or wgrad");
+  int r = ols_conv5x5_route(d, (int)IC, (int)OC, (int)H, (int)W);
+  return r == 0 ? "direct" : r == 1 ? "mfma" : "two_stage";
+}
+
 at::Tensor conv5x5_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
                        at::Tensor ntab, bool relu) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 5);
@@ -423,12 +436,9 @@ at::Tensor conv5x5_wgrad(at::Tensor x, at::Tensor dy, at::Tensor ntab) {
   // q-chains stay latency-serial.  wgrad is the one conv5 direction
   // with a real GEMM shape (K = B*OH*OW = 1600) — the MFMA kernel
   // stays.  Kept behind OLSIM_CONV5=direct for the record.
-  const size_t lds1 = ((size_t)IC * H * W
-                       + (size_t)OC * (H - 4) * (W - 4)) * sizeof(short);
-  const char* c5 = getenv("OLSIM_CONV5");
   at::Tensor part;
   float* partp = nullptr;
-  if (lds1 <= 32768 && c5 != nullptr && c5[0] == 'd') {
+  if (ols_conv5x5_route(2, IC, OC, H, W) == 2) {
     part = at::empty({(int64_t)C * B * OC * IC * 25},
                      x.options().dtype(at::kFloat));
     partp = part.data_ptr<float>();
@@ -732,6 +742,8 @@ at::Tensor transpose2d(at::Tensor x) {
               x.scalar_type() == at::kFloat);
   int64_t B = x.size(0);
   int M = x.size(1), N = x.size(2);
+  // the batch is the grid's z dimension in both kernels
+  TORCH_CHECK(B <= 65535, "transpose2d: batch ", B, " exceeds 65535");
   auto y = at::empty({B, (int64_t)N, (int64_t)M}, x.options());
   int dt = x.scalar_type() == at::kBFloat16 ? 1 : 0;
   ols_transpose2d(x.data_ptr(), y.data_ptr(), B, M, N, dt,
@@ -761,6 +773,8 @@ TORCH_LIBRARY(olsim_hip, m) {
   m.def("conv3x3_fwd_p(Tensor xp, Tensor w, int stride) -> Tensor");
   m.def("conv3x3_dgrad_p(Tensor dyp, Tensor w, int H, int W, int stride) -> Tensor");
   m.def("conv3x3_wgrad_p(Tensor xp, Tensor dy, int stride) -> Tensor");
+  m.def("conv5x5_route(str dir, int IC, int OC, int H, int W) -> str",
+        &conv5x5_route);
   m.def("conv5x5_fwd(Tensor x, Tensor w, Tensor bias, Tensor ntab, bool relu) -> Tensor");
   m.def("conv5x5_dgrad(Tensor dyp, Tensor w, Tensor ntab, int H, int W) -> Tensor");
   m.def("conv5x5_wgrad(Tensor x, Tensor dy, Tensor ntab) -> Tensor");

@@ -334,6 +334,70 @@ __global__ __launch_bounds__(CV5_THREADS) void k_conv5x5_wgrad(
 static inline int cdiv5(int a, int b) { return (a + b - 1) / b; }
 static inline int xcd_blocks5(int C, int T) { return ((C + 7) / 8 * 8) * T; }
 
+// ---------------------------------------------------------------------------
+// Route decisions, one host function per direction.  The launchers below
+// and the binding's conv5x5_route() both go through these, so a test can
+// assert the kernel a shape runs.  OLSIM_CONV5 is read on every call:
+// "mfma" forces the implicit-GEMM kernels, "direct" additionally selects
+// the two-stage weight gradient.  H, W are the x plane in all three.
+enum { CV5_DIRECT = 0, CV5_MFMA = 1, CV5_TWO_STAGE = 2 };
+#define CV5_DIRECT_LDS 32768
+
+static inline char conv5_env() {
+  const char* c5 = getenv("OLSIM_CONV5");
+  return c5 == nullptr ? '\0' : c5[0];
+}
+
+// LDS bytes of the direct fwd: the x plane of every input channel plus
+// the client's weights
+static inline size_t conv5_fwd_direct_lds(int IC, int OC, int H, int W) {
+  return ((size_t)IC * H * W + (size_t)OC * IC * 25) * sizeof(short);
+}
+
+// direct dgrad: the dy plane padded by 4 of every output channel plus
+// the (flipped) weights
+static inline size_t conv5_dgrad_direct_lds(int IC, int OC, int H, int W) {
+  return ((size_t)OC * (H + 4) * (W + 4) + (size_t)OC * IC * 25)
+         * sizeof(short);
+}
+
+// two-stage wgrad stage 1: the x planes plus the dy planes of one image
+static inline size_t conv5_wgrad_part_lds(int IC, int OC, int H, int W) {
+  return ((size_t)IC * H * W + (size_t)OC * (H - 4) * (W - 4))
+         * sizeof(short);
+}
+
+static int conv5_route_fwd(int IC, int OC, int H, int W) {
+  // the register-blocked kernel reads x rows as u32 pairs: W even, and
+  // its 4-wide column blocks need OW >= 4
+  if (conv5_fwd_direct_lds(IC, OC, H, W) <= CV5_DIRECT_LDS && W - 4 >= 4
+      && W % 2 == 0 && conv5_env() != 'm')
+    return CV5_DIRECT;
+  return CV5_MFMA;
+}
+
+static int conv5_route_dgrad(int IC, int OC, int H, int W) {
+  // dX plane W and padded dy plane W + 4 both even
+  if (conv5_dgrad_direct_lds(IC, OC, H, W) <= CV5_DIRECT_LDS && W >= 4
+      && W % 2 == 0 && (W + 4) % 2 == 0 && conv5_env() != 'm')
+    return CV5_DIRECT;
+  return CV5_MFMA;
+}
+
+static int conv5_route_wgrad(int IC, int OC, int H, int W) {
+  if (conv5_wgrad_part_lds(IC, OC, H, W) <= CV5_DIRECT_LDS
+      && conv5_env() == 'd')
+    return CV5_TWO_STAGE;
+  return CV5_MFMA;
+}
+
+// dir: 0 fwd, 1 dgrad, 2 wgrad
+extern "C" int ols_conv5x5_route(int dir, int IC, int OC, int H, int W) {
+  if (dir == 0) return conv5_route_fwd(IC, OC, H, W);
+  if (dir == 1) return conv5_route_dgrad(IC, OC, H, W);
+  return conv5_route_wgrad(IC, OC, H, W);
+}
+
 
 // ---------------------------------------------------------------------------
 // Direct VALU forward.  PMC on the implicit-GEMM fwd: MFMA busy 1.4%,
@@ -438,11 +502,8 @@ extern "C" void ols_conv5x5_fwd(const void* x, const void* w, const void* b,
   // one-output-per-thread version was 3-4x SLOWER — single dependent
   // ds_read chain; the register blocking is what wins.)
   // OLSIM_CONV5=mfma restores the MFMA path.
-  const size_t direct_lds = ((size_t)IC * H * W + (size_t)OC * g.K)
-                            * sizeof(short);
-  const char* c5 = getenv("OLSIM_CONV5");
-  if (direct_lds <= 32768 && g.OW >= 4 && W % 2 == 0
-      && (c5 == nullptr || c5[0] != 'm')) {
+  if (conv5_route_fwd(IC, OC, H, W) == CV5_DIRECT) {
+    const size_t direct_lds = conv5_fwd_direct_lds(IC, OC, H, W);
     dim3 gridd((unsigned)((int64_t)C * B));
     if (relu)
       hipLaunchKernelGGL((k_conv5x5_fwd_direct<true>), gridd,
@@ -556,11 +617,8 @@ extern "C" void ols_conv5x5_dgrad(const void* dyp, const void* w, void* dx,
   g.tiles_n = cdiv5(B * H * W, CV5_BN);
   // direct register-blocked kernel (see fwd): OLSIM_CONV5=mfma falls
   // back to the implicit GEMM
-  const size_t direct_lds = ((size_t)OC * g.H * g.W
-                             + (size_t)OC * IC * 25) * sizeof(short);
-  const char* c5 = getenv("OLSIM_CONV5");
-  if (direct_lds <= 32768 && g.OW >= 4 && g.OW % 2 == 0 && g.W % 2 == 0
-      && (c5 == nullptr || c5[0] != 'm')) {
+  if (conv5_route_dgrad(IC, OC, H, W) == CV5_DIRECT) {
+    const size_t direct_lds = conv5_dgrad_direct_lds(IC, OC, H, W);
     dim3 gridd((unsigned)((int64_t)C * B));
     hipLaunchKernelGGL(k_conv5x5_dgrad_direct, gridd, dim3(CV5_THREADS),
                        direct_lds, stream, (const __hip_bfloat16*)dyp,
@@ -748,11 +806,10 @@ extern "C" void ols_conv5x5_wgrad(const void* x, const void* dy, void* dw,
   g.IC = IC; g.OC = OC; g.C = C;
   g.K = 0; g.KP = 0;
   g.tiles_n = cdiv5(IC * 25, CV5_BN);
-  if (part != nullptr) {
-    // two-stage direct path: binding allocated the [C, B, ntaps] fp32
-    // partial buffer after checking the same LDS/shape conditions
-    const size_t lds1 = ((size_t)IC * H * W
-                         + (size_t)OC * g.OH * g.OW) * sizeof(short);
+  if (part != nullptr && conv5_route_wgrad(IC, OC, H, W) == CV5_TWO_STAGE) {
+    // two-stage direct path: the binding allocates the [C, B, ntaps] fp32
+    // partial buffer exactly when conv5_route_wgrad says two-stage
+    const size_t lds1 = conv5_wgrad_part_lds(IC, OC, H, W);
     hipLaunchKernelGGL(k_conv5x5_wgrad_part, dim3((unsigned)((int64_t)C * B)),
                        dim3(CV5_THREADS), lds1, stream,
                        (const __hip_bfloat16*)x, (const __hip_bfloat16*)dy,
@@ -769,12 +826,12 @@ extern "C" void ols_conv5x5_wgrad(const void* x, const void* dy, void* dw,
   // at C<=6250 for 256 CUs x many waves) and each tap's 1600-deep
   // q-loop is FMA-latency serial.  The MFMA implicit GEMM keeps wgrad
   // (K = B*OH*OW = 1600 is the one conv5 direction with a real GEMM
-  // shape).  Kept behind OLSIM_CONV5=direct for the record.
-  const size_t direct_lds = ((size_t)IC * H * W
-                             + (size_t)OC * g.OH * g.OW) * sizeof(short);
-  const char* c5 = getenv("OLSIM_CONV5");
-  if (direct_lds <= 32768 && OC * IC * 25 <= 10 * CV5_THREADS
-      && c5 != nullptr && c5[0] == 'd') {
+  // shape).  Kept behind OLSIM_CONV5=direct for the record.  Unreachable
+  // through the binding: its condition implies conv5_route_wgrad ==
+  // two-stage, for which the binding always passes a partial buffer.
+  const size_t direct_lds = conv5_wgrad_part_lds(IC, OC, H, W);
+  if (direct_lds <= CV5_DIRECT_LDS && OC * IC * 25 <= 10 * CV5_THREADS
+      && conv5_env() == 'd') {
     hipLaunchKernelGGL(k_conv5x5_wgrad_direct, dim3((unsigned)C),
                        dim3(CV5_THREADS), direct_lds, stream,
                        (const __hip_bfloat16*)x, (const __hip_bfloat16*)dy,

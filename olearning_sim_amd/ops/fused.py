@@ -374,8 +374,9 @@ def groupnorm_relu_pad(x: torch.Tensor, clients: int, groups: int,
 def fast_transpose(x: torch.Tensor) -> torch.Tensor:
     """[B, M, N] -> contiguous [B, N, M] via the LDS-tiled transpose
     kernel (torch's transpose+contiguous runs the generic strided copy
-    at a fraction of the roofline on large batched matrices)."""
-    if x.is_cuda and x.dim() == 3 and \
+    at a fraction of the roofline on large batched matrices).  The
+    kernels put the batch on grid.z, so a batch past 65535 goes to torch."""
+    if x.is_cuda and x.dim() == 3 and x.shape[0] <= 65535 and \
             x.dtype in (torch.bfloat16, torch.float32):
         ops = load_hip_ops()
         if ops is not None:

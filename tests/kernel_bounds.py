@@ -27,6 +27,10 @@ kernel received, and accepts
   reference value of 1e-70 (softmax tail at logits +-80) is legitimately
   returned as 0.
 
+An operation whose input was itself computed inexactly (the second
+rounding of bmm + bias, the tied head's rounded logits) adds the
+propagated error as an absolute ``extra`` term, derived at the call.
+
 These numbers are derived, not fitted: a kernel that exceeds them is a
 finding.  The module also holds the dtype-generic math of the checked
 operations, run in fp64 as the reference and (by the CPU tests) in fp32
@@ -53,14 +57,17 @@ def upcast(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(device="cpu", dtype=torch.float64)
 
 
-def bound(ref, scale, n, out_dtype, intrinsic=False, roundings=1):
+def bound(ref, scale, n, out_dtype, intrinsic=False, roundings=1, extra=0.0):
+    """``extra`` is an absolute allowance (scalar or tensor like ref) for
+    error the operation inherits from an input that was itself computed
+    inexactly; the caller derives it.  0 leaves the bound as documented."""
     rel = (n + 2) * U_ACC + (U_INTRINSIC if intrinsic else 0.0)
     return (roundings * U_OUT[out_dtype] * ref.abs() + rel * scale
-            + FTZ_FLOOR)
+            + FTZ_FLOOR + extra)
 
 
 def assert_bounded(got, ref, scale, n, out_dtype, intrinsic=False,
-                   where=None, label="", roundings=1):
+                   where=None, label="", roundings=1, extra=0.0):
     """Assert |got - ref| <= bound element-wise (optionally only ``where``).
     Returns the worst error as a fraction of its bound."""
     got = upcast(got)
@@ -69,7 +76,7 @@ def assert_bounded(got, ref, scale, n, out_dtype, intrinsic=False,
     assert got.shape == ref.shape, (label, tuple(got.shape), tuple(ref.shape))
     assert bool(torch.isfinite(got).all()), f"{label}: non-finite output"
     bnd = bound(ref, scale.expand_as(ref) if scale.dim() else scale, n,
-                out_dtype, intrinsic, roundings)
+                out_dtype, intrinsic, roundings, extra)
     ratio = (got - ref).abs() / bnd
     if where is not None:
         ratio = torch.where(where, ratio, torch.zeros_like(ratio))
@@ -302,3 +309,259 @@ def delta_math(delta, buf, master, weights, offsets, clients, hoisted=False):
         scale_h[g0:g1] += ((blk.abs() * wv.abs()).sum(0)
                            + wv.abs().sum() * m.abs().squeeze(0))
     return out, scale, scale_h
+
+
+# ---------------------------------------------------------------------------
+# per-client linear (models/base.py _BLinearFn)
+
+def linear_math(x, w, b, dy, mutant=None):
+    """y = x @ w [+ b] and the gradients for upstream dy, in x.dtype:
+    x [C, rows, in], w [C, in, out], b [C, out] or None, dy [C, rows, out].
+    Returns y, dx, dw, db, the bias-free product xw, and the abs-value
+    scale of each.  Mutants: dw from the untransposed operand (x's memory
+    reinterpreted as [C, in, rows]), db dropped, dx off by 1 %."""
+    C, rows, fin = x.shape
+    xw = torch.bmm(x, w)
+    xw_scale = torch.bmm(x.abs(), w.abs())
+    y, y_scale = xw, xw_scale
+    if b is not None:
+        y = xw + b.unsqueeze(1)
+        y_scale = xw_scale + b.abs().unsqueeze(1)
+    dx = torch.bmm(dy, w.transpose(1, 2))
+    if mutant == "dx_1pct":
+        dx = dx * 1.01
+    xt = x.transpose(1, 2)
+    if mutant == "dw_untransposed":
+        xt = x.contiguous().view(C, fin, rows)
+    dw = torch.bmm(xt, dy)
+    db = dy.sum(dim=1)
+    if mutant == "db_dropped":
+        db = torch.zeros_like(db)
+    return {"y": y, "y_scale": y_scale, "xw": xw, "xw_scale": xw_scale,
+            "dx": dx, "dx_scale": torch.bmm(dy.abs(), w.abs().transpose(1, 2)),
+            "dw": dw, "dw_scale": torch.bmm(x.abs().transpose(1, 2), dy.abs()),
+            "db": db, "db_scale": dy.abs().sum(dim=1)}
+
+
+def assert_linear_bounded(got, ref, dtype, has_bias, label="blinear"):
+    """got: dict y/dx/dw[/db] of a per-client linear; ref: linear_math in
+    fp64 on upcast operands.  Reduction lengths: y in, dx out, dw rows,
+    db rows.
+
+    With a bias the forward is ``bmm`` (stored in ``dtype``: error
+    e1 <= u|xw| + (in+2) 2^-23 |x||w|) followed by an add that is rounded
+    again, relative to the sum it formed: u|xw + e1 + b| <= u|y| + u|e1|.
+    Total: u|y| + (in+2) 2^-23 |x||w| + u|xw| + u|e1|.  The first two are
+    the ordinary bound of y; the rest is passed as ``extra``.  It is
+    relative to |xw|, not |y|: xw and b can cancel, so ``roundings=2``
+    (2u|y|) would be wrong."""
+    rows, fin = ref["dx"].shape[1], ref["dx"].shape[2]
+    fout = ref["y"].shape[2]
+    extra = 0.0
+    if has_bias:
+        u = U_OUT[dtype]
+        extra = u * (ref["xw"].abs()
+                     + bound(ref["xw"], ref["xw_scale"], fin, dtype))
+    assert_bounded(got["y"], ref["y"], ref["y_scale"], fin, dtype,
+                   label=label + ".y", extra=extra)
+    assert_bounded(got["dx"], ref["dx"], ref["dx_scale"], fout, dtype,
+                   label=label + ".dx")
+    assert_bounded(got["dw"], ref["dw"], ref["dw_scale"], rows, dtype,
+                   label=label + ".dw")
+    if has_bias:
+        assert_bounded(got["db"], ref["db"], ref["db_scale"], rows, dtype,
+                       label=label + ".db")
+
+
+# ---------------------------------------------------------------------------
+# tied LM head + cross-entropy (models/bert.py _TiedHeadCE)
+
+def tied_head_math(hs, tok, bias, labels, slice_v):
+    """Full-logits form of mean_n CE(hs @ tok^T + bias, labels) in
+    hs.dtype: hs [C, N, H], tok [C, V, H], bias [C, V], labels [C, N].
+    Returns loss, dhs, dtok, dbias for upstream 1 and the intermediate
+    and abs-value quantities the bound needs.  ``slice_v`` only groups
+    the abs-value partial sums of dhs the way the sliced code forms
+    them; the values do not depend on it."""
+    C, N, H = hs.shape
+    V = tok.shape[1]
+    g = 1.0 / (C * N)
+    z0 = torch.bmm(hs, tok.transpose(1, 2))              # [C, N, V]
+    z = z0 + bias.unsqueeze(1)
+    z_scale = torch.bmm(hs.abs(), tok.abs().transpose(1, 2)) \
+        + bias.abs().unsqueeze(1)
+    ce = ce_math(z.reshape(C * N, V), labels.reshape(C * N))
+    p = (z - z.logsumexp(dim=2, keepdim=True)).exp()
+    onehot = torch.zeros_like(p)
+    onehot.scatter_(2, labels.unsqueeze(2), 1.0)
+    dl = g * (p - onehot)
+    dl_scale = g * (p + onehot)
+    part_abs = torch.zeros_like(hs)
+    for s0 in range(0, V, slice_v):
+        s1 = min(s0 + slice_v, V)
+        part_abs = part_abs + torch.bmm(dl[:, :, s0:s1], tok[:, s0:s1]).abs()
+    return {"loss": ce["loss"], "loss_scale": ce["loss_scale"],
+            "z0": z0, "z_scale": z_scale, "p": p, "dl": dl,
+            "dl_scale": dl_scale, "g": g,
+            "dhs": torch.bmm(dl, tok), "dhs_scale": torch.bmm(dl_scale, tok.abs()),
+            "dhs_part_abs": part_abs,
+            "dtok": torch.bmm(dl.transpose(1, 2), hs),
+            "dtok_scale": torch.bmm(dl_scale.transpose(1, 2), hs.abs()),
+            "dbias": dl.sum(dim=1), "dbias_scale": dl_scale.sum(dim=1)}
+
+
+def assert_tied_head_bounded(got, ref, hs, tok, dtype, slice_v, label="tied"):
+    """got: dict loss/dhs/dtok/dbias of the sliced tied head; ref:
+    tied_head_math in fp64 on upcast operands (hs, tok also upcast).
+
+    Rounding points of _TiedHeadCE, in order:
+
+    1. Each logit is a bmm output stored in ``dtype`` before ``.float()``
+       and the fp32 bias add: |dz| <= d_z = bound(hs.tok, |hs||tok| +
+       |bias|, H+1, dtype).  d = max_j d_z per row.
+    2. lse is 1-Lipschitz in the max norm and z_y moves by at most d, so
+       a row loss moves by at most 2d, plus its fp32 evaluation over V
+       terms; the mean over C*N rows is one more fp32 sum.  torch.exp /
+       torch.log are correctly rounded library calls, not fast
+       intrinsics: no intrinsic term.
+    3. p_j = exp(z_j - lse): both move by at most d, so |dp_j| <=
+       p_j (e^{2d} - 1).  dlogits = g (p - onehot) is evaluated in fp32
+       (length-V term on g (p + onehot)) and stored in ``dtype``: one
+       rounding, of the perturbed value.  E_dl is the sum of the three.
+    4. dbias and dtok sum N perturbed dlogits (times |hs| for dtok):
+       the propagated sum of E_dl, the fp32 sum (N+2) 2^-23 scale, one
+       output rounding.
+    5. dhs = sum over S slices of a GEMM whose output is stored in
+       ``dtype`` (one rounding per partial), accumulated by ``dhs +=``
+       in ``dtype`` starting from zero (the first add is exact, the other
+       S-1 round once each).  Every rounded quantity is at most
+       (1+u)^(2S-1) sum_s |partial_s|, so: (2S-1) u (1+u)^(2S-1)
+       sum_s |partial_s|, plus the propagated sum of E_dl |tok| and the
+       fp32 sum over V.  The output rounding is one of those (2S-1)."""
+    C, N, H = hs.shape
+    V = tok.shape[1]
+    S = (V + slice_v - 1) // slice_v
+    u = U_OUT[dtype]
+    g = ref["g"]
+    d_z = bound(ref["z0"], ref["z_scale"], H + 1, dtype)
+    d = d_z.max(dim=2, keepdim=True).values                     # [C, N, 1]
+    assert_bounded(got["loss"], ref["loss"], ref["loss_scale"], V + C * N,
+                   torch.float32, label=label + ".loss",
+                   extra=float((2 * d).mean()))
+    dp = g * ref["p"] * torch.expm1(2 * d)
+    e_dl = bound(ref["dl"], ref["dl_scale"], V, dtype) + (1 + u) * dp
+    assert_bounded(got["dbias"], ref["dbias"], ref["dbias_scale"], N, dtype,
+                   label=label + ".dbias", extra=e_dl.sum(dim=1))
+    assert_bounded(got["dtok"], ref["dtok"], ref["dtok_scale"], N, dtype,
+                   label=label + ".dtok",
+                   extra=torch.bmm(e_dl.transpose(1, 2), hs.abs()))
+    assert_bounded(got["dhs"], ref["dhs"], ref["dhs_scale"], V, dtype,
+                   label=label + ".dhs", roundings=0,
+                   extra=((2 * S - 1) * u * (1 + u) ** (2 * S - 1)
+                          * ref["dhs_part_abs"]
+                          + torch.bmm(e_dl, tok.abs())))
+
+
+# ---------------------------------------------------------------------------
+# model-level gradients: device fp32 against the same model in fp64
+
+MODEL_CASES = {
+    # name -> (constructor kwargs, clients, batch, k): k = fast-intrinsic
+    # custom-kernel calls on the GPU path - the HIP cross-entropy for MLP
+    # and LSTM; BERT's tied head uses no fast intrinsic but each of its
+    # 1 + 2*layers LayerNorms does.
+    "mlp": (dict(in_features=40, hidden=24, num_classes=10), 3, 8, 1),
+    "lstm": (dict(vocab_size=30, embed=8, hidden=16, layers=2, seq_len=4),
+             3, 8, 1),
+    "bert": (dict(seq_len=8, vocab_size=40, hidden=32, layers=2, heads=2),
+             3, 4, 5),
+}
+_MODEL_CACHE: dict = {}
+
+
+def _rel_max(g, g64):
+    return float((g.detach().double().cpu() - g64).abs().max()
+                 / g64.abs().max())
+
+
+def model_loss_and_grads(model, params, x, y):
+    """model.loss and its gradient per parameter tensor."""
+    leaves = {k: v.detach().clone().requires_grad_(True)
+              for k, v in params.items()}
+    loss = model.loss(leaves, x, y)
+    grads = torch.autograd.grad(loss, list(leaves.values()))
+    return loss.detach(), dict(zip(leaves, grads))
+
+
+def model_case(name):
+    """Model, per-client perturbed fp32 parameters (the values every path
+    receives), inputs, the fp64 reference and e_cpu32; built once.
+
+    The fp64 reference runs the model's CPU forward on fp64 copies and
+    takes the cross-entropy through ce_math in fp64 (the CPU
+    cross_entropy_fwd_bwd casts its logits to fp32).  e_cpu32 is the
+    worst max|g - g64| / max|g64| over the loss and all parameter
+    gradients of the CPU fp32 composed path."""
+    if name in _MODEL_CACHE:
+        return _MODEL_CACHE[name]
+    from olearning_sim_amd.models import build_model
+    kwargs, C, B, k = MODEL_CASES[name]
+    model = build_model(name, **kwargs)
+    gen = torch.Generator().manual_seed(17)
+    gp = model.init_global(generator=gen)
+    params = {}
+    for key, v in gp.items():
+        rep = v.float().unsqueeze(0).expand(C, *v.shape).clone()
+        params[key] = rep + 0.01 * torch.randn(rep.shape, generator=gen)
+    if model.sequence_model:
+        V, L = model.vocab_size, model.seq_len
+        x = torch.randint(0, V, (C, B, L), generator=gen)
+        y = torch.randint(0, V, (C, B, L), generator=gen)
+    else:
+        x = torch.randn((C, B) + tuple(model.input_shape), generator=gen)
+        y = torch.randint(0, model.num_classes, (C, B), generator=gen)
+
+    p64 = {key: v.double().requires_grad_(True) for key, v in params.items()}
+    logits = model.forward(p64, x if model.sequence_model else x.double())
+    K = logits.shape[-1]
+    loss64 = ce_math(logits.reshape(-1, K), y.reshape(-1))["loss"]
+    g64 = dict(zip(p64, torch.autograd.grad(loss64, list(p64.values()))))
+    loss64 = loss64.detach()
+    for key, g in g64.items():
+        assert float(g.abs().max()) > 0, f"{name}: {key} has a zero gradient"
+
+    loss32, g32 = model_loss_and_grads(model, params, x, y)
+    e_cpu32 = max([abs(float(loss32) - float(loss64)) / abs(float(loss64))]
+                  + [_rel_max(g32[key], g64[key]) for key in g64])
+    case = {"model": model, "params": params, "x": x, "y": y, "k": k,
+            "loss64": loss64, "g64": g64, "e_cpu32": e_cpu32}
+    _MODEL_CACHE[name] = case
+    return case
+
+
+def assert_model_bounded(name, loss, grads):
+    """Loss and every parameter gradient within
+    tol = 64 * k * max(e_cpu32, 2^-22) of fp64, relative to the largest
+    reference element of the tensor.
+
+    e_cpu32 is what the plain fp32 composition of the same model loses
+    against fp64 (floored at one fp32 output unit); a HIP kernel may use
+    fast intrinsics, whose unit U_INTRINSIC is 64 x U_OUT[float32], and k
+    such kernels sit on the path.  Nothing here is read off the code
+    under test.  Returns the worst e / tol."""
+    case = model_case(name)
+    tol = (U_INTRINSIC / U_OUT[torch.float32]) * case["k"] \
+        * max(case["e_cpu32"], U_OUT[torch.float32])
+    errs = {"loss": abs(float(loss) - float(case["loss64"]))
+            / abs(float(case["loss64"]))}
+    for key, g64 in case["g64"].items():
+        assert bool(torch.isfinite(grads[key]).all()), f"{name}: {key}"
+        errs[key] = _rel_max(grads[key], g64)
+    worst = max(errs, key=errs.get)
+    ratio = errs[worst] / tol
+    HEADROOM["model." + name] = max(HEADROOM.get("model." + name, 0.0), ratio)
+    print(f"model[{name}] e_cpu32 = {case['e_cpu32']:.2e}, tol = {tol:.2e}, "
+          f"worst e/tol = {ratio:.4f} ({worst})")
+    bad = {key: f"{e / tol:.1f}x" for key, e in errs.items() if not e <= tol}
+    assert not bad, f"{name}: beyond tol {tol:.2e}: {bad}"
+    return ratio

@@ -1,7 +1,8 @@
 """conv3x3 (every kernel family and dispatch branch), conv5x5 and the
 2x2 max-pool against fp64 references with the derived bounds of
 tests/kernel_bounds.py.  Each conv3x3 case asserts the family the
-dispatcher takes, so a silent change of route fails here."""
+dispatcher takes and each conv5x5 case the route of all three
+directions, so a silent change of route fails here."""
 
 import pytest
 import torch
@@ -38,8 +39,11 @@ def _conv3_case(shape):
     return _REF_CACHE[shape]
 
 
-def _check_conv3x3(shape, v6, tag):
-    from olearning_sim_amd.ops.conv import client_conv3x3
+def _check_conv3x3(shape, v6, tag, forced_v5=False):
+    """forced_v5: OLSIM_CONV_V=5 is set, which ops.conv3x3_v6_ok (the
+    shape predicate) ignores; the dispatcher's own _v6_ok must then say
+    v5 for a shape of the v6 family."""
+    from olearning_sim_amd.ops.conv import client_conv3x3, _v6_ok
     from olearning_sim_amd.ops.fused import load_hip_ops
     ops = load_hip_ops(required=True)
     C, IC, OC, B, H, W, s = shape
@@ -48,6 +52,8 @@ def _check_conv3x3(shape, v6, tag):
     x, w, dy, ref = _conv3_case(shape)
     xg = x.cuda().requires_grad_(True)
     wg = w.cuda().requires_grad_(True)
+    assert _v6_ok(ops, xg, wg, s) == (v6 and not forced_v5), \
+        f"{shape}: dispatcher takes the wrong family"
     y = client_conv3x3(xg, wg, s)
     y.backward(dy.cuda())
     OH, OW = y.shape[-2:]
@@ -79,6 +85,13 @@ V5_SHAPES = [
     # odd planes at stride 2 (7 -> 4): v6 and dgrad_v5 assume H = 2*OH
     (2, 64, 64, 2, 7, 7, 2),
     (2, 64, 64, 2, 7, 8, 2),
+    (1, 3, 64, 1, 32, 32, 1),      # IC = 3 stem: fwd_v2 + dgrad_v5, stride 1
+]
+# v6-family shapes run under OLSIM_CONV_V=5: fwd_v5<true> and dgrad_v5 at
+# stride 1 and stride 2
+FORCED_V5_SHAPES = [
+    (1, 64, 64, 1, 32, 32, 1),
+    (2, 64, 128, 2, 16, 16, 2),
 ]
 
 
@@ -110,17 +123,71 @@ def test_conv3x3_env_gated_kernels_bounded(shape, var, monkeypatch):
     _check_conv3x3(shape, True, "conv3." + var.rsplit("_", 1)[1].lower())
 
 
+@pytest.mark.parametrize("shape", FORCED_V5_SHAPES, ids=str)
+def test_conv3x3_forced_v5_kernels_bounded(shape, monkeypatch):
+    """The pipelined v5 kernels a v6-family shape gets under
+    OLSIM_CONV_V=5 (the A/B switch).  The family assertion goes through
+    the dispatcher's _v6_ok, which reads the variable."""
+    for other in ("OLSIM_CONV_V8", "OLSIM_CONV_DW64", "OLSIM_CONV_DW8"):
+        monkeypatch.delenv(other, raising=False)
+    monkeypatch.setenv("OLSIM_CONV_V", "5")
+    _check_conv3x3(shape, True, "conv3.forced_v5", forced_v5=True)
+
+
 # ---------------------------------------------------------------------------
 # conv5x5
 
+# (shape, OLSIM_CONV5, expected fwd / dgrad / wgrad route); shapes are
+# (C, IC, OC, B, H, W) with B*(H-4)*(W-4) % 32 == 0.  LDS needs in bytes:
+# fwd 2*(IC*H*W + OC*IC*25), dgrad 2*(OC*(H+4)*(W+4) + OC*IC*25), two-stage
+# wgrad 2*(IC*H*W + OC*(H-4)*(W-4)); the direct limit is 32768.
+CONV5_CASES = [
+    # non-square plane and the IC = OC = 16 limit
+    ((2, 4, 8, 2, 12, 20), None, "direct", "direct", "mfma"),
+    ((2, 16, 16, 2, 12, 12), None, "direct", "direct", "mfma"),
+    # odd W: no u32 row reads.  fwd N = 288 = 2*128 + 32 and dgrad
+    # N = 624 = 4*128 + 112, so both MFMA tile tails run; K = 100 -> 128
+    ((2, 4, 8, 4, 12, 13), None, "mfma", "mfma", "mfma"),
+    # fwd needs 39168 B; dgrad 27136 B stays direct
+    ((1, 16, 8, 2, 32, 32), None, "mfma", "direct", "mfma"),
+    # fwd 32376 B, just inside; dgrad 41496 B
+    ((1, 12, 13, 2, 32, 32), None, "direct", "mfma", "mfma"),
+    ((2, 4, 8, 2, 12, 20), "mfma", "mfma", "mfma", "mfma"),
+    ((2, 16, 16, 2, 12, 12), "mfma", "mfma", "mfma", "mfma"),
+    ((2, 6, 16, 8, 14, 14), "mfma", "mfma", "mfma", "mfma"),
+    ((2, 4, 8, 2, 12, 20), "direct", "direct", "direct", "two_stage"),
+    ((2, 16, 16, 2, 12, 12), "direct", "direct", "direct", "two_stage"),
+    # two-stage wgrad needs 45312 B: back to the MFMA wgrad
+    ((1, 16, 8, 2, 32, 32), "direct", "mfma", "direct", "mfma"),
+]
+
+
+def _conv5_id(case):
+    return str(case[0]) if case[1] is None else f"{case[0]}:{case[1]}"
+
+
 @pytest.mark.parametrize("relu", [False, True])
-@pytest.mark.parametrize("shape", [(2, 4, 8, 2, 12, 20), (2, 16, 16, 2, 12, 12)],
-                         ids=str)
-def test_conv5x5_bounded(shape, relu):
-    """Non-square plane and the IC = OC = 16 limit.  ReLU: signs the
-    fp64 pre-activation cannot decide follow the kernel's own mask."""
+@pytest.mark.parametrize("case", CONV5_CASES, ids=_conv5_id)
+def test_conv5x5_bounded(case, relu, monkeypatch):
+    """Every conv5x5 route, with the route asserted through the host
+    functions the launchers branch on (the launchers read OLSIM_CONV5 on
+    every call).  The two-stage weight gradient still reduces over
+    B*OH*OW and the bound covers any summation order, so it needs no term
+    of its own.  ReLU: signs the fp64 pre-activation cannot decide follow
+    the kernel's own mask."""
+    from olearning_sim_amd.ops import load_hip_ops
     from olearning_sim_amd.ops.conv import client_conv5x5, conv5x5_supported
+    shape, env, r_fwd, r_dgrad, r_wgrad = case
+    if env is None:
+        monkeypatch.delenv("OLSIM_CONV5", raising=False)
+    else:
+        monkeypatch.setenv("OLSIM_CONV5", env)
+    ops = load_hip_ops(required=True)
     C, IC, OC, B, H, W = shape
+    assert (B * (H - 4) * (W - 4)) % 32 == 0
+    assert ops.conv5x5_route("fwd", IC, OC, H, W) == r_fwd
+    assert ops.conv5x5_route("dgrad", IC, OC, H, W) == r_dgrad
+    assert ops.conv5x5_route("wgrad", IC, OC, H, W) == r_wgrad
     g = torch.Generator().manual_seed(11)
     x = (torch.randn(C, IC, B, H, W, generator=g) * 0.5).to(BF)
     w = (torch.randn(C, OC, IC, 5, 5, generator=g) * 0.1).to(BF)

@@ -232,3 +232,229 @@ def test_delta_accum_emulation_passes_weight_mutant_fails(dtype, C):
                         offs, C, hoisted=True)[0]
     _rejects(bad, ref, scale, C + 1, F32)
     _rejects(bad, ref, scale_h, C + 1, F32)
+
+
+# -- per-client linear ------------------------------------------------------
+
+def _linear_standin(x, w, b, dy, dtype, mutant=None):
+    """fp32 math, rounded to ``dtype`` where _BLinearFn rounds: the bmm
+    output, then (with a bias) the sum again."""
+    r = kb.linear_math(x.float(), w.float(), None if b is None else b.float(),
+                       dy.float(), mutant=mutant)
+    y = r["xw"].to(dtype)
+    if b is not None:
+        y = (y.float() + b.float().unsqueeze(1)).to(dtype)
+    return {"y": y, "dx": r["dx"].to(dtype), "dw": r["dw"].to(dtype),
+            "db": r["db"].to(dtype)}
+
+
+@pytest.mark.parametrize("dtype", [F32, BF])
+@pytest.mark.parametrize("has_bias", [True, False])
+def test_blinear_emulation_passes_mutants_fail(dtype, has_bias):
+    g = torch.Generator().manual_seed(6)
+    C, rows, fin, fout = 3, 8, 40, 24
+    x = torch.randn(C, rows, fin, generator=g).to(dtype)
+    w = (torch.randn(C, fin, fout, generator=g) * 0.2).to(dtype)
+    b = torch.randn(C, fout, generator=g).to(dtype) if has_bias else None
+    dy = (torch.randn(C, rows, fout, generator=g) * 0.1).to(dtype)
+    ref = kb.linear_math(upcast(x), upcast(w),
+                         None if b is None else upcast(b), upcast(dy))
+    kb.assert_linear_bounded(_linear_standin(x, w, b, dy, dtype), ref, dtype,
+                             has_bias)
+    mutants = ["dw_untransposed", "dx_1pct"] + (["db_dropped"] if has_bias
+                                                else [])
+    for mutant in mutants:
+        with pytest.raises(AssertionError):
+            kb.assert_linear_bounded(
+                _linear_standin(x, w, b, dy, dtype, mutant), ref, dtype,
+                has_bias)
+
+
+def test_blinear_bias_needs_its_own_rounding_term():
+    """Where x@w and b cancel, the first rounding is large against |y|:
+    the derived ``extra`` accepts the honest kernel, two roundings
+    relative to |y| would not."""
+    g = torch.Generator().manual_seed(8)
+    C, rows, fin, fout = 2, 8, 16, 32
+    x = torch.randn(C, rows, fin, generator=g).to(BF)
+    w = torch.randn(C, fin, fout, generator=g).to(BF)
+    xw = torch.bmm(x.float(), w.float())
+    b = (-xw[:, 0] + 0.01).to(BF)            # row 0 of every client cancels
+    dy = torch.randn(C, rows, fout, generator=g).to(BF)
+    ref = kb.linear_math(upcast(x), upcast(w), upcast(b), upcast(dy))
+    got = _linear_standin(x, w, b, dy, BF)
+    kb.assert_linear_bounded(got, ref, BF, True)
+    _rejects(got["y"], ref["y"], ref["y_scale"], fin, BF, roundings=2)
+
+
+# -- transposes -------------------------------------------------------------
+
+@pytest.mark.parametrize("N", [64, 90, 400, 218])
+def test_thin_transpose_chunking_emulation_is_exact(N):
+    """k_transpose_thin's decomposition: 128-column chunks, each written
+    as out[n0:n0+nn, :M]."""
+    x = torch.randn(3, 24, N).to(BF)
+    out = torch.empty(3, N, 24, dtype=BF)
+    for n0 in range(0, N, 128):
+        nn = min(128, N - n0)
+        out[:, n0:n0 + nn] = x[:, :, n0:n0 + nn].transpose(1, 2)
+    assert torch.equal(out, x.transpose(1, 2).contiguous())
+
+
+# -- 1x1 conv, stride 2 -----------------------------------------------------
+
+def test_conv1x1_stride2_emulation_passes_odd_pixel_mutant_fails():
+    g = torch.Generator().manual_seed(10)
+    C, IC, OC, B, H, W = 2, 16, 32, 2, 8, 8
+    x = (torch.randn(C, IC, B, H, W, generator=g) * 0.5).to(BF)
+    w = (torch.randn(C, OC, IC, generator=g) * 0.1).to(BF)
+    dy = (torch.randn(C, OC, B, 4, 4, generator=g) * 0.1).to(BF)
+    ref = kb.conv_ref(upcast(x), upcast(w).view(C, OC, IC, 1, 1), upcast(dy),
+                      2, 0)
+
+    def emu(off):
+        xs = x.float()[..., off::2, off::2].reshape(C, IC, B * 16)
+        return torch.bmm(w.float(), xs).view(C, OC, B, 4, 4).to(BF)
+
+    assert_bounded(emu(0), ref["y"], ref["y_scale"], IC, BF, label="conv1.y")
+    _rejects(emu(1), ref["y"], ref["y_scale"], IC, BF)   # pixel (2i+1, 2j+1)
+
+
+# -- tied head + cross-entropy ----------------------------------------------
+
+def _tied_head_sliced(hs, tok, bias, labels, sv, dtype, mutant=None):
+    """_TiedHeadCE's algorithm in fp32 torch with its roundings to
+    ``dtype``: online-softmax forward over vocabulary slices, backward
+    recomputing each slice.  Mutants: "skip_last" (last slice never
+    visited), "wrong_slice" (the label's -1 lands in the next slice),
+    "overwrite" (dhs = instead of dhs +=)."""
+    C, N, H = hs.shape
+    V = tok.shape[1]
+    f = lambda t: t.float()
+    rd = lambda t: t.to(dtype).float()
+    starts = list(range(0, V, sv))
+    if mutant == "skip_last":
+        starts = starts[:-1]
+
+    def logits_of(s0, s1):
+        return rd(torch.bmm(f(hs), f(tok)[:, s0:s1].transpose(1, 2))) \
+            + f(bias)[:, s0:s1].unsqueeze(1)
+
+    m = torch.full((C, N), float("-inf"))
+    l = torch.zeros(C, N)
+    zy = torch.zeros(C, N)
+    for s0 in starts:
+        s1 = min(s0 + sv, V)
+        z = logits_of(s0, s1)
+        m_new = torch.maximum(m, z.max(dim=2).values)
+        l = l * torch.exp(m - m_new) + torch.exp(z - m_new.unsqueeze(2)).sum(2)
+        m = m_new
+        sel = (labels >= s0) & (labels < s1)
+        idx = (labels - s0).clamp(0, s1 - s0 - 1)
+        zy = torch.where(sel, z.gather(2, idx.unsqueeze(2)).squeeze(2), zy)
+    loss = (torch.log(l) + m - zy).mean()
+
+    g = 1.0 / (C * N)
+    lse = (m + torch.log(l)).unsqueeze(2)
+    dhs = torch.zeros(C, N, H)
+    dtok = torch.zeros(C, V, H)
+    dbias = torch.zeros(C, V)
+    for s0 in starts:
+        s1 = min(s0 + sv, V)
+        p = torch.exp(logits_of(s0, s1) - lse)
+        lab = labels + sv if mutant == "wrong_slice" else labels
+        lab = torch.where(lab >= V, lab - sv * len(starts), lab)
+        sel = (lab >= s0) & (lab < s1)
+        idx = (lab - s0).clamp(0, s1 - s0 - 1)
+        p = p - torch.zeros_like(p).scatter_(2, idx.unsqueeze(2), 1.0) \
+            * sel.unsqueeze(2)
+        dl = rd(p * g)
+        dbias[:, s0:s1] = rd(dl.sum(dim=1))
+        part = rd(torch.bmm(dl, f(tok)[:, s0:s1]))
+        dhs = part if mutant == "overwrite" else rd(dhs + part)
+        dtok[:, s0:s1] = rd(torch.bmm(dl.transpose(1, 2), f(hs)))
+    return {"loss": loss, "dhs": dhs.to(dtype), "dtok": dtok.to(dtype),
+            "dbias": dbias.to(dtype)}
+
+
+@pytest.mark.parametrize("dtype", [F32, BF])
+def test_tied_head_emulation_passes_mutants_fail(dtype):
+    g = torch.Generator().manual_seed(23)
+    C, N, H, V, sv = 2, 8, 16, 40, 16
+    hs = torch.randn(C, N, H, generator=g).to(dtype)
+    tok = (torch.randn(C, V, H, generator=g) * 0.5).to(dtype)
+    bias = (torch.randn(C, V, generator=g) * 0.5).to(dtype)
+    labels = torch.tensor([[0, 15, 16, 31, 32, 39, 7, 20],
+                           [39, 32, 31, 16, 15, 0, 33, 8]])
+    ref = kb.tied_head_math(upcast(hs), upcast(tok), upcast(bias), labels, sv)
+    args = (ref, upcast(hs), upcast(tok), dtype, sv)
+    kb.assert_tied_head_bounded(
+        _tied_head_sliced(hs, tok, bias, labels, sv, dtype), *args)
+    # the model's own implementation, which also runs on the CPU
+    from olearning_sim_amd.models.bert import _TiedHeadCE, tied_head_ce
+    leaves = [t.clone().requires_grad_(True) for t in (hs, tok, bias)]
+    old = _TiedHeadCE.SLICE_V
+    _TiedHeadCE.SLICE_V = sv
+    try:
+        loss = tied_head_ce(*leaves, labels)
+        loss.backward()
+    finally:
+        _TiedHeadCE.SLICE_V = old
+    kb.assert_tied_head_bounded(
+        {"loss": loss.detach(), "dhs": leaves[0].grad,
+         "dtok": leaves[1].grad, "dbias": leaves[2].grad}, *args,
+        label="tied.model")
+    for mutant in ("skip_last", "wrong_slice", "overwrite"):
+        with pytest.raises(AssertionError):
+            kb.assert_tied_head_bounded(
+                _tied_head_sliced(hs, tok, bias, labels, sv, dtype, mutant),
+                *args)
+
+
+# -- model gradients --------------------------------------------------------
+
+class _BLinearStandIn(torch.autograd.Function):
+    """_BLinearFn's forward and hand-written backward on the CPU, with an
+    optional 1 % error in one of the three gradients."""
+    mutant = None
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        y = torch.bmm(x, w)
+        return y if b is None else y + b.unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        k = {m: 1.01 if _BLinearStandIn.mutant == m else 1.0
+             for m in ("dx", "dw", "db")}
+        dx = k["dx"] * torch.bmm(dy, w.transpose(1, 2).contiguous())
+        dw = k["dw"] * torch.bmm(x.transpose(1, 2).contiguous(), dy)
+        db = k["db"] * dy.sum(dim=1) if ctx.has_bias else None
+        return dx, dw, db
+
+
+@pytest.mark.parametrize("name", ["mlp", "lstm", "bert"])
+def test_model_gradient_check_accepts_standin_rejects_1pct(name, monkeypatch):
+    import importlib
+    case = kb.model_case(name)
+    assert 0 < case["e_cpu32"] < 1e-5
+    mod = importlib.import_module("olearning_sim_amd.models." + name)
+    monkeypatch.setattr(
+        mod, "blinear",
+        lambda x, w, b=None: _BLinearStandIn.apply(x.contiguous(),
+                                                   w.contiguous(), b))
+
+    def run(mutant):
+        monkeypatch.setattr(_BLinearStandIn, "mutant", mutant)
+        loss, grads = kb.model_loss_and_grads(case["model"], case["params"],
+                                              case["x"], case["y"])
+        return kb.assert_model_bounded(name, loss, grads)
+
+    run(None)
+    for mutant in ("dx", "dw", "db"):
+        with pytest.raises(AssertionError):
+            run(mutant)

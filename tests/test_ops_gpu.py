@@ -266,6 +266,65 @@ def test_transpose2d_matches_torch(shape):
         torch.testing.assert_close(y, ref, atol=0, rtol=0)
 
 
+def _thin_route(M):
+    """ols_transpose2d's predicate for k_transpose_thin."""
+    return M <= 32 and M % 8 == 0
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=str)
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("M", [8, 16, 24, 32])
+@pytest.mark.parametrize("N", [64, 90, 400, 218])
+def test_transpose2d_thin_route_exact(N, M, B, dt):
+    """k_transpose_thin, the route of every activation transpose at batch
+    8..32.  N = 64: one packed chunk; 90: the scalar load branch; 400:
+    three full 128-column chunks and a packed 16-wide tail; 218: a full
+    chunk loaded packed from rows that are not 16-byte aligned, then a
+    scalar 90-wide tail.  A copy is exact or wrong."""
+    from olearning_sim_amd.ops import load_hip_ops
+    ops = load_hip_ops(required=True)
+    assert _thin_route(M)
+    g = torch.Generator().manual_seed(N * 64 + M)
+    x = torch.randn(B, M, N, generator=g).to(dt).cuda()
+    y = ops.transpose2d(x)
+    assert y.shape == (B, N, M) and y.is_contiguous() and y.dtype == dt
+    assert torch.equal(y, x.transpose(1, 2).contiguous())
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=str)
+@pytest.mark.parametrize("shape", [(2, 12, 64), (2, 40, 64)], ids=str)
+def test_transpose2d_thin_predicate_edges_stay_tiled(shape, dt):
+    """M = 12 (not a multiple of 8) and M = 40 (past 32) sit just outside
+    the thin predicate and must be right on the tiled kernel's edge path."""
+    from olearning_sim_amd.ops import load_hip_ops
+    ops = load_hip_ops(required=True)
+    assert not _thin_route(shape[1])
+    g = torch.Generator().manual_seed(shape[1])
+    x = torch.randn(*shape, generator=g).to(dt).cuda()
+    y = ops.transpose2d(x)
+    assert y.is_contiguous()
+    assert torch.equal(y, x.transpose(1, 2).contiguous())
+
+
+def test_transpose2d_rejects_batch_past_grid_limit():
+    """The batch is grid.z (limit 65535) in both kernels: the wrapper must
+    raise on the host before any launch, and fast_transpose must hand such
+    a batch to torch instead."""
+    from olearning_sim_amd.ops import load_hip_ops
+    from olearning_sim_amd.ops.fused import fast_transpose
+    ops = load_hip_ops(required=True)
+    x = torch.arange(65536 * 64, device="cuda", dtype=torch.float32) \
+        .view(65536, 8, 8).to(torch.bfloat16)
+    with pytest.raises(RuntimeError, match="65535"):
+        ops.transpose2d(x)
+    torch.cuda.synchronize()
+    y = fast_transpose(x)
+    assert y.is_contiguous()
+    assert torch.equal(y, x.transpose(1, 2).contiguous())
+    ok = ops.transpose2d(x[:65535])
+    assert torch.equal(ok, x[:65535].transpose(1, 2).contiguous())
+
+
 @pytest.mark.parametrize("shape", [(5, 64, 16, 32, 32), (2, 3, 4, 8, 8),
                                    (7, 16, 16)])
 def test_subsample2_matches_slicing(shape):
