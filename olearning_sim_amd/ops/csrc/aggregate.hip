@@ -13,6 +13,7 @@
 // replica dtype.
 
 #include "common.h"
+#include "ols_ops.h"
 
 #define MAX_LDS_W 4096
 

@@ -6,130 +6,7 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 
-#include "groupnorm.h"
-
-extern "C" void ols_fused_sgd_update_flat(
-    void* buf, const void* grad, const void* master, const int64_t* offs,
-    int nblocks, int64_t clients, int64_t total, float lr, float mu,
-    int dtype, hipStream_t stream);
-
-extern "C" void ols_weighted_delta_accum_flat(
-    float* delta, const void* buf, const void* master, const float* weights,
-    const int64_t* offs, int nblocks, int64_t clients, int64_t pglobal,
-    float wsum, int dtype, hipStream_t stream);
-
-extern "C" void ols_cross_entropy_fwd_bwd(
-    const void* logits, const int64_t* labels, float* loss, void* dlogits,
-    int64_t nrows, int64_t K, float inv_n, int dtype, hipStream_t stream);
-
-extern "C" void ols_groupnorm_fwd(const void* x, const void* res, void* y,
-                                  float* mean, float* rstd, const void* gamma,
-                                  const void* beta, int B, int C, int ch,
-                                  int G, int HW, float eps, bool relu,
-                                  int layout, int dtype, hipStream_t stream);
-
-extern "C" void ols_mfma_selftest(const void* A, const void* B, float* D,
-                                  hipStream_t stream);
-
-extern "C" void ols_conv3x3_fwd(const void* x, const void* w, void* y, int C,
-                                int IC, int OC, int B, int H, int W,
-                                int stride, hipStream_t stream);
-extern "C" void ols_conv3x3_dgrad(const void* dy, const void* w, void* dx,
-                                  int C, int IC, int OC, int B, int H, int W,
-                                  int stride, hipStream_t stream);
-extern "C" void ols_conv3x3_wgrad(const void* x, const void* dy, void* dw,
-                                  int C, int IC, int OC, int B, int H, int W,
-                                  int stride, hipStream_t stream);
-
-extern "C" int ols_conv3x3_v6_ok(int IC, int OC, int B, int H, int W,
-                                 int stride);
-extern "C" void ols_conv3x3_fwd_p(const void* xp, const void* w, void* y,
-                                  int C, int IC, int OC, int B, int H, int W,
-                                  int stride, hipStream_t stream);
-extern "C" void ols_conv3x3_dgrad_p(const void* dyp, const void* w, void* dx,
-                                    int C, int IC, int OC, int B, int H,
-                                    int W, int stride, hipStream_t stream);
-extern "C" void ols_conv3x3_wgrad_p(const void* xp, const void* dy, void* dw,
-                                    int C, int IC, int OC, int B, int H,
-                                    int W, int stride, hipStream_t stream);
-
-extern "C" void ols_conv5x5_fwd(const void* x, const void* w, const void* b,
-                                void* y, const int* ntab, int C, int IC,
-                                int OC, int B, int H, int W, int relu,
-                                hipStream_t stream);
-extern "C" void ols_conv5x5_dgrad(const void* dyp, const void* w, void* dx,
-                                  const int* ntab, int C, int IC, int OC,
-                                  int B, int H, int W, hipStream_t stream);
-extern "C" int ols_conv5x5_route(int dir, int IC, int OC, int H, int W);
-extern "C" void ols_conv5x5_wgrad(const void* x, const void* dy, void* dw,
-                                  float* part, const int* ntab, int C,
-                                  int IC, int OC, int B, int H, int W,
-                                  hipStream_t stream);
-
-extern "C" void ols_pool2x2_fwd(const void* x, void* y, unsigned char* arg,
-                                int64_t planes, int OH, int OW, int dtype,
-                                hipStream_t stream);
-extern "C" void ols_pool2x2_bwd(const void* dy, const unsigned char* arg,
-                                void* dx, int64_t planes, int OH, int OW,
-                                int dtype, hipStream_t stream);
-
-extern "C" void ols_subsample2_fwd(const void* x, void* y, int64_t planes,
-                                   int OH, int OW, int dtype,
-                                   hipStream_t stream);
-extern "C" void ols_subsample2_bwd(const void* dy, void* dx, int64_t planes,
-                                   int H, int W, int dtype,
-                                   hipStream_t stream);
-
-extern "C" void ols_transpose2d(const void* in, void* out, int64_t B, int M,
-                                int N, int dtype, hipStream_t stream);
-
-extern "C" void ols_pad2d(const void* in, void* out, int64_t planes, int H,
-                          int W, int pad, int dtype, hipStream_t stream);
-
-extern "C" void ols_replicate(const void* src, void* dst, int64_t clients,
-                              int64_t n, int dtype, hipStream_t stream);
-
-extern "C" void ols_synth_batch(const float* x, const int64_t* y, void* out,
-                                int64_t rows, int64_t batch, int64_t n,
-                                float s, float t, hipStream_t stream);
-
-extern "C" void ols_relu_mask(const void* dy, const void* y, void* out,
-                              int64_t n, int dtype, hipStream_t stream);
-
-extern "C" void ols_layernorm_fwd(const void* x, const void* gamma,
-                                  const void* beta, void* y, float* mean,
-                                  float* rstd, int64_t rows, int H,
-                                  int64_t rows_per_client, float eps,
-                                  int dtype, hipStream_t stream);
-extern "C" void ols_layernorm_bwd(const void* x, const void* dy,
-                                  const void* gamma, const float* mean,
-                                  const float* rstd, void* dx, float* dgamma,
-                                  float* dbeta, int64_t rows, int H,
-                                  int64_t rows_per_client, int dtype,
-                                  hipStream_t stream);
-
-extern "C" void ols_groupnorm_bwd(const void* x, const void* y,
-                                  const void* dy, void* dx, void* dres,
-                                  const float* mean, const float* rstd,
-                                  const void* gamma, float* dgamma,
-                                  float* dbeta, int B, int C, int ch, int G,
-                                  int HW, bool relu, int layout, int dtype,
-                                  hipStream_t stream);
-
-extern "C" int ols_gn_pad_ok(int ch, int G, int H, int W);
-extern "C" void ols_groupnorm_fwd_pad(
-    const void* x, const void* res, int res_mode, void* y, uint32_t* mask,
-    float* mean, float* rstd, const void* gamma, const void* beta, int B,
-    int C, int ch, int G, int H, int W, float eps, bool pad_out,
-    hipStream_t stream);
-extern "C" void ols_groupnorm_bwd_pad(
-    const void* x, const uint32_t* mask, const void* dy, void* dx,
-    void* dx_pad, void* dres, const float* mean, const float* rstd,
-    const void* gamma, float* dgamma, float* dbeta, int B, int C, int ch,
-    int G, int H, int W, hipStream_t stream);
-extern "C" void ols_subsample2p_fwd(const void* xp, void* y, int64_t planes,
-                                    int OH, int OW, int dtype,
-                                    hipStream_t stream);
+#include "ols_ops.h"
 
 namespace {
 
@@ -292,47 +169,91 @@ at::Tensor mfma_selftest(at::Tensor A, at::Tensor B) {
   return D;
 }
 
-// x: [C, IC, B, H, W] bf16; w: [C, OC, IC, 3, 3] bf16 -> y [C, OC, B, OH, OW]
+// ---- client-batched convolutions -----------------------------------------
+
+// Shape of one k x k conv call (k = 3: pad 1, stride 1 or 2; k = 5: valid,
+// stride 1), for all nine wrappers.  A call has two of the three operands
+//   x  [C, IC, B, H + 2*x_halo, W + 2*x_halo]
+//   dy [C, OC, B, OH + 2*dy_halo, OW + 2*dy_halo]
+//   w  [C, OC, IC, k, k]
+// and passes an undefined tensor for the third; H, W are read from x, or
+// given when x is absent (dgrad).  Every operand must be a contiguous 5-D
+// bf16 tensor on one device (the kernels reinterpret everything as bf16)
+// of exactly the size above, so C, IC, OC, B and the planes the kernels
+// index agree across the call.
+struct ConvDims {
+  int C, IC, OC, B, H, W, OH, OW;
+};
+
+ConvDims conv_dims(int k, const at::Tensor& x, int x_halo,
+                   const at::Tensor& dy, int dy_halo, const at::Tensor& w,
+                   int64_t H, int64_t W, int64_t stride) {
+  const at::Tensor& first = x.defined() ? x : dy;
+  for (const at::Tensor* t : {&x, &dy, &w}) {
+    if (!t->defined()) continue;
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 5 &&
+                    t->scalar_type() == at::kBFloat16 &&
+                    t->device() == first.device(),
+                "conv", k, "x", k, ": operands must be contiguous 5-D bf16 "
+                "tensors on one GPU");
+  }
+  TORCH_CHECK(stride == 1 || (k == 3 && stride == 2), "conv", k, "x", k,
+              ": stride ", stride, " unsupported");
+  if (x.defined()) {
+    H = x.size(3) - 2 * x_halo;
+    W = x.size(4) - 2 * x_halo;
+  }
+  const int64_t C = first.size(0), B = first.size(2);
+  const int64_t IC = x.defined() ? x.size(1) : w.size(2);
+  const int64_t OC = dy.defined() ? dy.size(1) : w.size(1);
+  const int64_t OH = k == 3 ? (H + stride - 1) / stride : H - 4;
+  const int64_t OW = k == 3 ? (W + stride - 1) / stride : W - 4;
+  TORCH_CHECK(C > 0 && IC > 0 && OC > 0 && B > 0 && OH > 0 && OW > 0,
+              "conv", k, "x", k, ": empty operand or plane");
+  auto expect = [&](const at::Tensor& t, const char* name,
+                    std::vector<int64_t> sizes) {
+    TORCH_CHECK(!t.defined() || t.sizes() == at::IntArrayRef(sizes), "conv",
+                k, "x", k, ": ", name, " is ", t.sizes(), ", expected ",
+                at::IntArrayRef(sizes));
+  };
+  expect(x, "x", {C, IC, B, H + 2 * x_halo, W + 2 * x_halo});
+  expect(dy, "dy", {C, OC, B, OH + 2 * dy_halo, OW + 2 * dy_halo});
+  expect(w, "w", {C, OC, IC, k, k});
+  return {(int)C, (int)IC, (int)OC, (int)B, (int)H, (int)W, (int)OH, (int)OW};
+}
+
+// ---- 3x3, v5 family (client_conv.hip): dense operands ----------------------
+
 at::Tensor conv3x3_fwd(at::Tensor x, at::Tensor w, int64_t stride) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 5);
-  TORCH_CHECK(w.is_contiguous() && w.dim() == 5 && w.size(3) == 3);
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
-              w.scalar_type() == at::kBFloat16);
-  int C = x.size(0), IC = x.size(1), B = x.size(2), H = x.size(3),
-      W = x.size(4), OC = w.size(1);
-  TORCH_CHECK(w.size(0) == C && w.size(2) == IC);
-  int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
-  auto y = at::empty({C, OC, B, OH, OW}, x.options());
-  ols_conv3x3_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), C, IC, OC, B, H,
-                  W, (int)stride, at::cuda::getCurrentCUDAStream().stream());
+  const ConvDims d = conv_dims(3, x, 0, {}, 0, w, 0, 0, stride);
+  auto y = at::empty({d.C, d.OC, d.B, d.OH, d.OW}, x.options());
+  ols_conv3x3_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), d.C, d.IC, d.OC,
+                  d.B, d.H, d.W, (int)stride,
+                  at::cuda::getCurrentCUDAStream().stream());
   return y;
 }
 
 at::Tensor conv3x3_dgrad(at::Tensor dy, at::Tensor w, int64_t H, int64_t W,
                          int64_t stride) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 5);
-  int C = dy.size(0), OC = dy.size(1), B = dy.size(2);
-  int IC = w.size(2);
-  auto dx = at::empty({C, IC, B, H, W}, dy.options());
-  ols_conv3x3_dgrad(dy.data_ptr(), w.contiguous().data_ptr(), dx.data_ptr(),
-                    C, IC, OC, B, (int)H, (int)W, (int)stride,
+  const ConvDims d = conv_dims(3, {}, 0, dy, 0, w, H, W, stride);
+  auto dx = at::empty({d.C, d.IC, d.B, d.H, d.W}, dy.options());
+  ols_conv3x3_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), d.C, d.IC,
+                    d.OC, d.B, d.H, d.W, (int)stride,
                     at::cuda::getCurrentCUDAStream().stream());
   return dx;
 }
 
 at::Tensor conv3x3_wgrad(at::Tensor x, at::Tensor dy, int64_t stride) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && dy.is_contiguous());
-  int C = x.size(0), IC = x.size(1), B = x.size(2), H = x.size(3),
-      W = x.size(4), OC = dy.size(1);
-  auto dw = at::empty({C, OC, IC, 3, 3}, x.options());
-  ols_conv3x3_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), C, IC,
-                    OC, B, H, W, (int)stride,
+  const ConvDims d = conv_dims(3, x, 0, dy, 0, {}, 0, 0, stride);
+  auto dw = at::empty({d.C, d.OC, d.IC, 3, 3}, x.options());
+  ols_conv3x3_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), d.C, d.IC,
+                    d.OC, d.B, d.H, d.W, (int)stride,
                     at::cuda::getCurrentCUDAStream().stream());
   return dw;
 }
 
-// ---- v6 padded family (client_conv2.hip) --------------------------------
-// x_pad: [C, IC, B, H+2, W+2] bf16 (1-element zero halo per plane)
+// ---- 3x3, v6 padded family (client_conv2.hip) ------------------------------
+// x_pad and dy_pad carry a 1-element zero halo per plane
 
 bool conv3x3_v6_ok(int64_t IC, int64_t OC, int64_t B, int64_t H, int64_t W,
                    int64_t stride) {
@@ -340,38 +261,53 @@ bool conv3x3_v6_ok(int64_t IC, int64_t OC, int64_t B, int64_t H, int64_t W,
                            (int)stride) != 0;
 }
 
-at::Tensor conv3x3_fwd_p(at::Tensor xp, at::Tensor w, int64_t stride) {
-  TORCH_CHECK(xp.is_cuda() && xp.is_contiguous() && xp.dim() == 5);
-  TORCH_CHECK(w.is_contiguous() && w.dim() == 5 && w.size(3) == 3);
-  TORCH_CHECK(xp.scalar_type() == at::kBFloat16 &&
-              w.scalar_type() == at::kBFloat16);
-  int C = xp.size(0), IC = xp.size(1), B = xp.size(2),
-      H = xp.size(3) - 2, W = xp.size(4) - 2, OC = w.size(1);
-  TORCH_CHECK(w.size(0) == C && w.size(2) == IC);
-  TORCH_CHECK(ols_conv3x3_v6_ok(IC, OC, B, H, W, (int)stride),
+// The kernel, with its template arguments, that x [*, IC, B, H, W] and OC
+// output channels run in direction dir ("fwd", "dgrad", "wgrad"), e.g.
+// "fwd_v7<5,1>".  Same host functions the launchers switch on, family
+// decision included; reads the OLSIM_CONV_* variables on every call.
+std::string conv3x3_route(std::string dir, int64_t IC, int64_t OC, int64_t B,
+                          int64_t H, int64_t W, int64_t stride) {
+  int d = dir == "fwd" ? 0 : dir == "dgrad" ? 1 : dir == "wgrad" ? 2 : -1;
+  TORCH_CHECK(d >= 0, "conv3x3_route: dir must be fwd, dgrad or wgrad");
+  TORCH_CHECK(stride == 1 || stride == 2, "conv3x3_route: stride 1 or 2");
+  return ols_conv3x3_route(d, (int)IC, (int)OC, (int)B, (int)H, (int)W,
+                           (int)stride);
+}
+
+void check_v6(const ConvDims& d, int64_t stride) {
+  TORCH_CHECK(ols_conv3x3_v6_ok(d.IC, d.OC, d.B, d.H, d.W, (int)stride),
               "shape unsupported by the v6 conv path");
-  int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
-  auto y = at::empty({C, OC, B, OH, OW}, xp.options());
-  ols_conv3x3_fwd_p(xp.data_ptr(), w.data_ptr(), y.data_ptr(), C, IC, OC, B,
-                    H, W, (int)stride,
+}
+
+at::Tensor conv3x3_fwd_p(at::Tensor xp, at::Tensor w, int64_t stride) {
+  const ConvDims d = conv_dims(3, xp, 1, {}, 0, w, 0, 0, stride);
+  check_v6(d, stride);
+  auto y = at::empty({d.C, d.OC, d.B, d.OH, d.OW}, xp.options());
+  ols_conv3x3_fwd_p(xp.data_ptr(), w.data_ptr(), y.data_ptr(), d.C, d.IC,
+                    d.OC, d.B, d.H, d.W, (int)stride,
                     at::cuda::getCurrentCUDAStream().stream());
   return y;
 }
 
-// dy_pad: [C, OC, B, OH+2, OW+2]; returns dx [C, IC, B, H, W]
 at::Tensor conv3x3_dgrad_p(at::Tensor dyp, at::Tensor w, int64_t H, int64_t W,
                            int64_t stride) {
-  TORCH_CHECK(dyp.is_cuda() && dyp.is_contiguous() && dyp.dim() == 5);
-  TORCH_CHECK(w.is_contiguous() && w.dim() == 5);
-  int C = dyp.size(0), OC = dyp.size(1), B = dyp.size(2);
-  int IC = w.size(2);
-  TORCH_CHECK(ols_conv3x3_v6_ok(IC, OC, B, H, W, (int)stride),
-              "shape unsupported by the v6 conv path");
-  auto dx = at::empty({C, IC, B, H, W}, dyp.options());
-  ols_conv3x3_dgrad_p(dyp.data_ptr(), w.data_ptr(), dx.data_ptr(), C, IC, OC,
-                      B, (int)H, (int)W, (int)stride,
+  const ConvDims d = conv_dims(3, {}, 0, dyp, 1, w, H, W, stride);
+  check_v6(d, stride);
+  auto dx = at::empty({d.C, d.IC, d.B, d.H, d.W}, dyp.options());
+  ols_conv3x3_dgrad_p(dyp.data_ptr(), w.data_ptr(), dx.data_ptr(), d.C, d.IC,
+                      d.OC, d.B, d.H, d.W, (int)stride,
                       at::cuda::getCurrentCUDAStream().stream());
   return dx;
+}
+
+at::Tensor conv3x3_wgrad_p(at::Tensor xp, at::Tensor dy, int64_t stride) {
+  const ConvDims d = conv_dims(3, xp, 1, dy, 0, {}, 0, 0, stride);
+  check_v6(d, stride);
+  auto dw = at::empty({d.C, d.OC, d.IC, 3, 3}, xp.options());
+  ols_conv3x3_wgrad_p(xp.data_ptr(), dy.data_ptr(), dw.data_ptr(), d.C, d.IC,
+                      d.OC, d.B, d.H, d.W, (int)stride,
+                      at::cuda::getCurrentCUDAStream().stream());
+  return dw;
 }
 
 // ---- 5x5 VALID family (client_conv5.hip, LeNet) -------------------------
@@ -389,76 +325,61 @@ std::string conv5x5_route(std::string dir, int64_t IC, int64_t OC, int64_t H,
   return r == 0 ? "direct" : r == 1 ? "mfma" : "two_stage";
 }
 
+// ntab has one int32 per position of the plane the kernel tiles over
+void check_ntab(const at::Tensor& ntab, const at::Tensor& on, int64_t n) {
+  TORCH_CHECK(ntab.is_cuda() && ntab.device() == on.device() &&
+                  ntab.scalar_type() == at::kInt && ntab.is_contiguous() &&
+                  ntab.numel() == n,
+              "conv5x5: ntab must be ", n, " contiguous int32 on the GPU");
+}
+
 at::Tensor conv5x5_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
                        at::Tensor ntab, bool relu) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 5);
-  TORCH_CHECK(w.is_contiguous() && w.dim() == 5 && w.size(3) == 5);
-  TORCH_CHECK(ntab.is_cuda() && ntab.scalar_type() == at::kInt &&
-              ntab.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16);
-  int C = x.size(0), IC = x.size(1), B = x.size(2), H = x.size(3),
-      W = x.size(4), OC = w.size(1);
-  TORCH_CHECK(w.size(0) == C && w.size(2) == IC && OC <= 16);
-  TORCH_CHECK(ntab.numel() == (int64_t)B * (H - 4) * (W - 4));
-  auto y = at::empty({C, OC, B, H - 4, W - 4}, x.options());
+  const ConvDims d = conv_dims(5, x, 0, {}, 0, w, 0, 0, 1);
+  TORCH_CHECK(d.OC <= 16);
+  check_ntab(ntab, x, (int64_t)d.B * d.OH * d.OW);
+  TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kBFloat16 &&
+              bias.numel() == (int64_t)d.C * d.OC);
+  auto y = at::empty({d.C, d.OC, d.B, d.OH, d.OW}, x.options());
   ols_conv5x5_fwd(x.data_ptr(), w.data_ptr(), bias.contiguous().data_ptr(),
-                  y.data_ptr(), ntab.data_ptr<int>(), C, IC, OC, B, H, W,
-                  relu ? 1 : 0, at::cuda::getCurrentCUDAStream().stream());
+                  y.data_ptr(), ntab.data_ptr<int>(), d.C, d.IC, d.OC, d.B,
+                  d.H, d.W, relu ? 1 : 0,
+                  at::cuda::getCurrentCUDAStream().stream());
   return y;
 }
 
-// dyp: [C,OC,B,OH+8,OW+8] (pad 4); returns dx [C,IC,B,H,W]
+// dyp: dy padded by 4, [C, OC, B, H+4, W+4]; returns dx [C, IC, B, H, W]
 at::Tensor conv5x5_dgrad(at::Tensor dyp, at::Tensor w, at::Tensor ntab,
                          int64_t H, int64_t W) {
-  TORCH_CHECK(dyp.is_cuda() && dyp.is_contiguous() && dyp.dim() == 5);
-  TORCH_CHECK(ntab.is_cuda() && ntab.scalar_type() == at::kInt);
-  int C = dyp.size(0), OC = dyp.size(1), B = dyp.size(2);
-  int IC = w.size(2);
-  TORCH_CHECK(IC <= 16 && ntab.numel() == (int64_t)B * H * W);
-  auto dx = at::empty({C, IC, B, H, W}, dyp.options());
-  ols_conv5x5_dgrad(dyp.data_ptr(), w.contiguous().data_ptr(), dx.data_ptr(),
-                    ntab.data_ptr<int>(), C, IC, OC, B, (int)H, (int)W,
+  const ConvDims d = conv_dims(5, {}, 0, dyp, 4, w, H, W, 1);
+  TORCH_CHECK(d.IC <= 16);
+  check_ntab(ntab, dyp, (int64_t)d.B * d.H * d.W);
+  auto dx = at::empty({d.C, d.IC, d.B, d.H, d.W}, dyp.options());
+  ols_conv5x5_dgrad(dyp.data_ptr(), w.data_ptr(), dx.data_ptr(),
+                    ntab.data_ptr<int>(), d.C, d.IC, d.OC, d.B, d.H, d.W,
                     at::cuda::getCurrentCUDAStream().stream());
   return dx;
 }
 
 at::Tensor conv5x5_wgrad(at::Tensor x, at::Tensor dy, at::Tensor ntab) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && dy.is_contiguous());
-  TORCH_CHECK(ntab.is_cuda() && ntab.scalar_type() == at::kInt);
-  int C = x.size(0), IC = x.size(1), B = x.size(2), H = x.size(3),
-      W = x.size(4), OC = dy.size(1);
-  TORCH_CHECK(OC <= 16 && ((int64_t)B * (H - 4) * (W - 4)) % 32 == 0);
-  auto dw = at::empty({C, OC, IC, 5, 5}, x.options());
-  // two-stage direct path (client_conv5.hip k_conv5x5_wgrad_part):
-  // per-(client, b) fp32 partials + a B-reduction.  MEASURED NEGATIVE
-  // (fedprox 96.9 vs 49.4 ms/round with the MFMA wgrad): the [C, B,
-  // ntaps] fp32 partial buffer is ~1 GB per call and the per-tap
-  // q-chains stay latency-serial.  wgrad is the one conv5 direction
-  // with a real GEMM shape (K = B*OH*OW = 1600) — the MFMA kernel
-  // stays.  Kept behind OLSIM_CONV5=direct for the record.
+  const ConvDims d = conv_dims(5, x, 0, dy, 0, {}, 0, 0, 1);
+  const int64_t nq = (int64_t)d.B * d.OH * d.OW;
+  TORCH_CHECK(d.OC <= 16 && nq % 32 == 0);
+  check_ntab(ntab, x, nq);
+  auto dw = at::empty({d.C, d.OC, d.IC, 5, 5}, x.options());
+  // The two-stage route (client_conv5.hip k_conv5x5_wgrad_part) needs a
+  // [C, B, ntaps] fp32 partial buffer; the launcher takes that route
+  // exactly when it gets one.
   at::Tensor part;
   float* partp = nullptr;
-  if (ols_conv5x5_route(2, IC, OC, H, W) == 2) {
-    part = at::empty({(int64_t)C * B * OC * IC * 25},
+  if (ols_conv5x5_route(2, d.IC, d.OC, d.H, d.W) == 2) {
+    part = at::empty({(int64_t)d.C * d.B * d.OC * d.IC * 25},
                      x.options().dtype(at::kFloat));
     partp = part.data_ptr<float>();
   }
   ols_conv5x5_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), partp,
-                    ntab.data_ptr<int>(), C, IC, OC, B, H, W,
+                    ntab.data_ptr<int>(), d.C, d.IC, d.OC, d.B, d.H, d.W,
                     at::cuda::getCurrentCUDAStream().stream());
-  return dw;
-}
-
-at::Tensor conv3x3_wgrad_p(at::Tensor xp, at::Tensor dy, int64_t stride) {
-  TORCH_CHECK(xp.is_cuda() && xp.is_contiguous() && dy.is_contiguous());
-  int C = xp.size(0), IC = xp.size(1), B = xp.size(2),
-      H = xp.size(3) - 2, W = xp.size(4) - 2, OC = dy.size(1);
-  TORCH_CHECK(ols_conv3x3_v6_ok(IC, OC, B, H, W, (int)stride),
-              "shape unsupported by the v6 conv path");
-  auto dw = at::empty({C, OC, IC, 3, 3}, xp.options());
-  ols_conv3x3_wgrad_p(xp.data_ptr(), dy.data_ptr(), dw.data_ptr(), C,
-                      IC, OC, B, H, W, (int)stride,
-                      at::cuda::getCurrentCUDAStream().stream());
   return dw;
 }
 
@@ -770,6 +691,8 @@ TORCH_LIBRARY(olsim_hip, m) {
   m.def("conv3x3_wgrad(Tensor x, Tensor dy, int stride) -> Tensor");
   m.def("conv3x3_v6_ok(int IC, int OC, int B, int H, int W, int stride) -> bool",
         &conv3x3_v6_ok);
+  m.def("conv3x3_route(str dir, int IC, int OC, int B, int H, int W, "
+        "int stride) -> str", &conv3x3_route);
   m.def("conv3x3_fwd_p(Tensor xp, Tensor w, int stride) -> Tensor");
   m.def("conv3x3_dgrad_p(Tensor dyp, Tensor w, int H, int W, int stride) -> Tensor");
   m.def("conv3x3_wgrad_p(Tensor xp, Tensor dy, int stride) -> Tensor");

@@ -25,6 +25,8 @@
 // through L2 instead of materialising a 9x patch matrix in HBM.
 
 #include "common.h"
+#include "conv3_route.h"
+#include "ols_ops.h"
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -88,93 +90,6 @@ __device__ __forceinline__ void n_decomp(const ConvGeom& g, int n, int& b,
     int q = n % OHW;
     oh = q / g.OW;
     ow = q % g.OW;
-  }
-}
-
-// stage the fwd/wgrad patch tile P[k][n] (k in [k0,k0+BK), n in
-// [n0,n0+BN)) into lds[BK][BN]; k=(ic,dh,dw) w/ dw fastest.
-template <int TILE_K, int TILE_N>
-__device__ void stage_patch(const __hip_bfloat16* __restrict__ x,
-                            short* lds, const ConvGeom g,
-                            int k0, int n0, int kmax, int nmax) {
-  const int HW = g.H * g.W;
-  const int OHW = g.OH * g.OW;
-  // each thread fills (TILE_K*TILE_N)/CONV_THREADS elements, n fastest
-  for (int i = threadIdx.x; i < TILE_K * TILE_N; i += CONV_THREADS) {
-    int kk = i / TILE_N, nn = i % TILE_N;
-    int k = k0 + kk, n = n0 + nn;
-    float v = 0.f;
-    if (k < kmax && n < nmax) {
-      int ic = k / 9, r = k % 9;
-      int dh = r / 3, dw = r % 3;
-      int b, oh, ow;
-      n_decomp(g, n, b, oh, ow);
-      int ih = oh * g.stride + dh - 1, iw = ow * g.stride + dw - 1;
-      if (ih >= 0 && ih < g.H && iw >= 0 && iw < g.W)
-        v = to_f32(x[((int64_t)ic * g.B + b) * HW + ih * g.W + iw]);
-    }
-    lds[kk * TILE_N + nn] = bf16_bits(v);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// forward: grid (ntiles_n, ntiles_m, C); x[C,IC,B,H,W] w[C,OC,IC,3,3]
-// y[C,OC,B,OH,OW]
-__global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd(
-    const __hip_bfloat16* __restrict__ x, const __hip_bfloat16* __restrict__ w,
-    __hip_bfloat16* __restrict__ y, ConvGeom g) {
-  __shared__ short a_lds[CONV_BM * CONV_BK];
-  __shared__ short b_lds[CONV_BK * CONV_BN];
-  const int c = blockIdx.z;
-  const int m0 = blockIdx.y * CONV_BM;
-  const int n0 = blockIdx.x * CONV_BN;
-  const int K = g.IC * 9;
-  const int N = g.B * g.OH * g.OW;
-  const __hip_bfloat16* xc = x + (int64_t)c * g.IC * g.B * g.H * g.W;
-  const __hip_bfloat16* wc = w + (int64_t)c * g.OC * K;
-  __hip_bfloat16* yc = y + (int64_t)c * g.OC * N;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;   // wave owns rows [m0+wave*16, +16)
-  f32x4 acc[CONV_BN / 16];
-#pragma unroll
-  for (int i = 0; i < CONV_BN / 16; ++i) acc[i] = {0.f, 0.f, 0.f, 0.f};
-
-  for (int k0 = 0; k0 < K; k0 += CONV_BK) {
-    // stage A = W[m0.., k0..]
-    for (int i = threadIdx.x; i < CONV_BM * CONV_BK; i += CONV_THREADS) {
-      int mm = i / CONV_BK, kk = i % CONV_BK;
-      int m = m0 + mm, k = k0 + kk;
-      a_lds[i] = (m < g.OC && k < K)
-                     ? bf16_bits(to_f32(wc[(int64_t)m * K + k])) : (short)0;
-    }
-    stage_patch<CONV_BK, CONV_BN>(xc, b_lds, g, k0, n0, K, N);
-    __syncthreads();
-
-    bf16x8 a = *reinterpret_cast<const bf16x8*>(
-        &a_lds[(wave * 16 + (lane & 15)) * CONV_BK + 8 * (lane >> 4)]);
-#pragma unroll
-    for (int nt = 0; nt < CONV_BN / 16; ++nt) {
-      bf16x8 b;
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        b[e] = b_lds[(8 * (lane >> 4) + e) * CONV_BN + nt * 16 + (lane & 15)];
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nt], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-
-  // write D: row = m0 + wave*16 + (lane>>4)*4 + r, col = n0 + nt*16 + (lane&15)
-#pragma unroll
-  for (int nt = 0; nt < CONV_BN / 16; ++nt) {
-    int n = n0 + nt * 16 + (lane & 15);
-    if (n >= N) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int m = m0 + wave * 16 + (lane >> 4) * 4 + r;
-      if (m < g.OC)
-        yc[(int64_t)m * N + n] = from_f32<__hip_bfloat16>(acc[nt][r]);
-    }
   }
 }
 
@@ -840,100 +755,82 @@ extern "C" void ols_mfma_selftest(const void* A, const void* B, float* D,
                      (const __hip_bfloat16*)A, (const __hip_bfloat16*)B, D);
 }
 
-static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// launchers: route (conv3_route.h), geometry, one switch
+
+static inline ConvGeom make_geom(int IC, int OC, int B, int H, int W,
+                                 int stride) {
+  ConvGeom g{B, H, W, conv3_cdiv(H, stride), conv3_cdiv(W, stride),
+             IC, OC, stride, 0, 0, 0};
+  if (conv3_is_p2(g.OW) && conv3_is_p2(g.OH)) {
+    g.lg_ow = conv3_lg(g.OW);
+    g.lg_ohw = conv3_lg(g.OW) + conv3_lg(g.OH);
+    g.pow2 = 1;
+  }
+  return g;
+}
+
+typedef void (*ConvKernel)(const __hip_bfloat16*, const __hip_bfloat16*,
+                           __hip_bfloat16*, ConvGeom);
+
+// grid (N tiles, M tiles, C) of an M x N output per client, tiled BM x BN
+static inline void launch(ConvKernel kernel, int M, int BM, int N, int BN,
+                          int C, const void* in, const void* w, void* out,
+                          const ConvGeom& g, hipStream_t stream) {
+  dim3 grid(conv3_cdiv(N, BN), conv3_cdiv(M, BM), C);
+  hipLaunchKernelGGL(kernel, grid, dim3(CONV_THREADS), 0, stream,
+                     (const __hip_bfloat16*)in, (const __hip_bfloat16*)w,
+                     (__hip_bfloat16*)out, g);
+}
 
 extern "C" void ols_conv3x3_fwd(const void* x, const void* w, void* y, int C,
                                 int IC, int OC, int B, int H, int W,
                                 int stride, hipStream_t stream) {
-  ConvGeom g{B, H, W, (H + stride - 1) / stride, (W + stride - 1) / stride,
-             IC, OC, stride, 0, 0, 0};
-  {
-    auto is_p2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-    auto lg = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    if (is_p2(g.OW) && is_p2(g.OH)) {
-      g.lg_ow = lg(g.OW);
-      g.lg_ohw = lg(g.OW) + lg(g.OH);
-      g.pow2 = 1;
-    }
+  const ConvGeom g = make_geom(IC, OC, B, H, W, stride);
+  ConvKernel k = nullptr;
+  switch (conv3_route_fwd_v5(IC, OC, B, H, W, stride)) {
+    case CV3_FWD_V2: k = k_conv3x3_fwd_v2; break;
+    case CV3_FWD_V5_TRUE: k = k_conv3x3_fwd_v5<true>; break;
+    case CV3_FWD_V5_FALSE: k = k_conv3x3_fwd_v5<false>; break;
+    default: return;                    // not a v5-family fwd route
   }
-  dim3 grid(ceil_div(B * g.OH * g.OW, CV2_BN), ceil_div(OC, CV2_BM), C);
-  const bool v5_ok = g.pow2 && ((IC * 9) % CV2_BK == 0);
-  if (v5_ok && g.OW >= CV2_BN / 8)
-    hipLaunchKernelGGL((k_conv3x3_fwd_v5<true>), grid, dim3(CONV_THREADS), 0,
-                       stream, (const __hip_bfloat16*)x,
-                       (const __hip_bfloat16*)w, (__hip_bfloat16*)y, g);
-  else if (v5_ok)
-    hipLaunchKernelGGL((k_conv3x3_fwd_v5<false>), grid, dim3(CONV_THREADS), 0,
-                       stream, (const __hip_bfloat16*)x,
-                       (const __hip_bfloat16*)w, (__hip_bfloat16*)y, g);
-  else
-    hipLaunchKernelGGL(k_conv3x3_fwd_v2, grid, dim3(CONV_THREADS), 0, stream,
-                       (const __hip_bfloat16*)x, (const __hip_bfloat16*)w,
-                       (__hip_bfloat16*)y, g);
+  launch(k, OC, CV2_BM, B * g.OH * g.OW, CV2_BN, C, x, w, y, g, stream);
 }
 
 extern "C" void ols_conv3x3_dgrad(const void* dy, const void* w, void* dx,
                                   int C, int IC, int OC, int B, int H, int W,
                                   int stride, hipStream_t stream) {
-  ConvGeom g{B, H, W, (H + stride - 1) / stride, (W + stride - 1) / stride,
-             IC, OC, stride, 0, 0, 0};
-  {
-    auto is_p2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-    auto lg = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    if (is_p2(g.OW) && is_p2(g.OH)) {
-      g.lg_ow = lg(g.OW);
-      g.lg_ohw = lg(g.OW) + lg(g.OH);
-      g.pow2 = 1;
-    }
-  }
-  // dgrad_v5 decomposes n with log2(W) = log2(OW * stride) and H == W:
-  // an odd plane at stride 2 (OH = ceil(H/2)) takes the generic kernel
-  const bool v5_ok = g.pow2 && ((OC * 9) % CV2_BK == 0)
-                     && (stride == 1 || stride == 2) && H == W
-                     && H == g.OH * stride;
-  if (v5_ok) {
-    dim3 grid5(ceil_div(B * H * W, CV2_BN), ceil_div(IC, CV2_BM), C);
-    if (stride == 1)
-      hipLaunchKernelGGL((k_conv3x3_dgrad_v5<1>), grid5, dim3(CONV_THREADS),
-                         0, stream, (const __hip_bfloat16*)dy,
-                         (const __hip_bfloat16*)w, (__hip_bfloat16*)dx, g);
-    else
-      hipLaunchKernelGGL((k_conv3x3_dgrad_v5<2>), grid5, dim3(CONV_THREADS),
-                         0, stream, (const __hip_bfloat16*)dy,
-                         (const __hip_bfloat16*)w, (__hip_bfloat16*)dx, g);
-  } else {
-    dim3 grid(ceil_div(B * H * W, CONV_BN), ceil_div(IC, CONV_BM), C);
-    hipLaunchKernelGGL(k_conv3x3_dgrad, grid, dim3(CONV_THREADS), 0, stream,
-                       (const __hip_bfloat16*)dy, (const __hip_bfloat16*)w,
-                       (__hip_bfloat16*)dx, g);
+  const ConvGeom g = make_geom(IC, OC, B, H, W, stride);
+  const int N = B * H * W;
+  switch (conv3_route_dgrad_v5(IC, OC, B, H, W, stride)) {
+    case CV3_DGRAD_GENERIC:
+      launch(k_conv3x3_dgrad, IC, CONV_BM, N, CONV_BN, C, dy, w, dx, g,
+             stream);
+      break;
+    case CV3_DGRAD_V5_1:
+      launch(k_conv3x3_dgrad_v5<1>, IC, CV2_BM, N, CV2_BN, C, dy, w, dx, g,
+             stream);
+      break;
+    case CV3_DGRAD_V5_2:
+      launch(k_conv3x3_dgrad_v5<2>, IC, CV2_BM, N, CV2_BN, C, dy, w, dx, g,
+             stream);
+      break;
+    default: break;                     // not a v5-family dgrad route
   }
 }
 
 extern "C" void ols_conv3x3_wgrad(const void* x, const void* dy, void* dw,
                                   int C, int IC, int OC, int B, int H, int W,
                                   int stride, hipStream_t stream) {
-  ConvGeom g{B, H, W, (H + stride - 1) / stride, (W + stride - 1) / stride,
-             IC, OC, stride, 0, 0, 0};
-  {
-    auto is_p2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-    auto lg = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    if (is_p2(g.OW) && is_p2(g.OH)) {
-      g.lg_ow = lg(g.OW);
-      g.lg_ohw = lg(g.OW) + lg(g.OH);
-      g.pow2 = 1;
-    }
-  }
-  const int NN = B * g.OH * g.OW;
-  const bool v5_ok = g.pow2 && (NN % CV2_BK == 0);
-  if (v5_ok) {
-    dim3 grid5(ceil_div(IC * 9, CV2_BN), ceil_div(OC, CV2_BM), C);
-    hipLaunchKernelGGL(k_conv3x3_wgrad_v5, grid5, dim3(CONV_THREADS), 0,
-                       stream, (const __hip_bfloat16*)x,
-                       (const __hip_bfloat16*)dy, (__hip_bfloat16*)dw, g);
-  } else {
-    dim3 grid(ceil_div(IC * 9, CONV_BN), ceil_div(OC, CONV_BM), C);
-    hipLaunchKernelGGL(k_conv3x3_wgrad, grid, dim3(CONV_THREADS), 0, stream,
-                       (const __hip_bfloat16*)x, (const __hip_bfloat16*)dy,
-                       (__hip_bfloat16*)dw, g);
+  const ConvGeom g = make_geom(IC, OC, B, H, W, stride);
+  switch (conv3_route_wgrad_v5(IC, OC, B, H, W, stride)) {
+    case CV3_WGRAD_GENERIC:
+      launch(k_conv3x3_wgrad, OC, CONV_BM, IC * 9, CONV_BN, C, x, dy, dw, g,
+             stream);
+      break;
+    case CV3_WGRAD_V5:
+      launch(k_conv3x3_wgrad_v5, OC, CV2_BM, IC * 9, CV2_BN, C, x, dy, dw, g,
+             stream);
+      break;
+    default: break;                     // not a v5-family wgrad route
   }
 }

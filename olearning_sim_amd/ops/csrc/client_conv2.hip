@@ -34,6 +34,8 @@
 // port; this is the MI355X-native design).
 
 #include "common.h"
+#include "conv3_route.h"
+#include "ols_ops.h"
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -1326,39 +1328,41 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_wgrad_v7(
 }
 
 // ---------------------------------------------------------------------------
-// launchers
+// launchers: route (conv3_route.h), geometry, one switch
 
-static inline int cdiv6(int a, int b) { return (a + b - 1) / b; }
-
+// H x W is the unpadded plane the kernel gathers from; OH x OW the plane
+// it tiles over.  tiles_m / tiles_n are the caller's.
 static inline void fill_geom6(ConvGeom6& g, int C, int IC, int OC, int B,
                               int H, int W, int stride) {
   g.B = B; g.Hp = H + 2; g.Wp = W + 2;
-  g.OH = (H + stride - 1) / stride; g.OW = (W + stride - 1) / stride;
+  g.OH = conv3_cdiv(H, stride); g.OW = conv3_cdiv(W, stride);
   g.IC = IC; g.OC = OC; g.stride = stride; g.C = C;
-  auto lg = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-  g.lg_ow = lg(g.OW);
-  g.lg_ohw = lg(g.OW) + lg(g.OH);
+  g.lg_ow = conv3_lg(g.OW);
+  g.lg_ohw = conv3_lg(g.OW) + conv3_lg(g.OH);
 }
 
-static inline int xcd_blocks6(int C, int T) {
-  return ((C + 7) / 8 * 8) * T;
+// every v6-family kernel has this signature, block size and no dynamic LDS
+typedef void (*ConvKernel6)(const __hip_bfloat16*, const __hip_bfloat16*,
+                            __hip_bfloat16*, ConvGeom6);
+
+// grid: XCD-padded (xcd_remap6) over the geometry's tiles
+static inline void launch6(ConvKernel6 kernel, const void* in, const void* w,
+                           void* out, const ConvGeom6& g,
+                           hipStream_t stream) {
+  dim3 grid(((g.C + 7) / 8 * 8) * (g.tiles_m * g.tiles_n));
+  hipLaunchKernelGGL(kernel, grid, dim3(CONV_THREADS), 0, stream,
+                     (const __hip_bfloat16*)in, (const __hip_bfloat16*)w,
+                     (__hip_bfloat16*)out, g);
 }
 
-// 1 when the v6 padded path supports the shape (pow2 planes, K%32==0)
 extern "C" int ols_conv3x3_v6_ok(int IC, int OC, int B, int H, int W,
                                  int stride) {
-  auto p2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-  int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
-  if (!p2(OH) || !p2(OW) || OW < 4) return 0;
-  // stride-2 dgrad scatters into a 2*OH x 2*OW dX plane: odd H or W
-  // (7 -> 4) would index dy_pad and dx with the wrong plane sizes
-  if (stride == 2 && ((H | W) & 1)) return 0;
-  if ((IC * 9) % CV6_BK != 0) return 0;             // fwd K
-  if ((OC * 9) % CV6_BK != 0) return 0;             // dgrad K (s=1)
-  if (stride == 2 && OC % CV6_BK != 0) return 0;    // smallest s2 class K=OC
-  if (stride != 1 && stride != 2) return 0;
-  if ((B * OH * OW) % CV6_BK != 0) return 0;        // wgrad A-direct rows
-  return 1;
+  return conv3_v6_ok(IC, OC, B, H, W, stride);
+}
+
+extern "C" const char* ols_conv3x3_route(int dir, int IC, int OC, int B,
+                                         int H, int W, int stride) {
+  return conv3_route_name(conv3_route(dir, IC, OC, B, H, W, stride));
 }
 
 extern "C" void ols_conv3x3_fwd_p(const void* xp, const void* w, void* y,
@@ -1366,122 +1370,66 @@ extern "C" void ols_conv3x3_fwd_p(const void* xp, const void* w, void* y,
                                   int stride, hipStream_t stream) {
   ConvGeom6 g;
   fill_geom6(g, C, IC, OC, B, H, W, stride);
-  g.tiles_m = cdiv6(OC, CV6_BM);
-  g.tiles_n = cdiv6(B * g.OH * g.OW, CV6_BN);
-  dim3 grid(xcd_blocks6(C, g.tiles_m * g.tiles_n));
-  auto xb = (const __hip_bfloat16*)xp;
-  auto wb = (const __hip_bfloat16*)w;
-  auto yb = (__hip_bfloat16*)y;
-#define LAUNCH_FWD6(LG, ST) \
-  hipLaunchKernelGGL((k_conv3x3_fwd_v6<LG, ST>), grid, dim3(CONV_THREADS), \
-                     0, stream, xb, wb, yb, g)
-#define LAUNCH_FWD7(LG, ST) \
-  hipLaunchKernelGGL((k_conv3x3_fwd_v7<LG, ST>), grid, dim3(CONV_THREADS), \
-                     0, stream, xb, wb, yb, g)
-  // BK=64 (v7) wins +5..10% at OW >= 8 stride 1 (A/B: gpurun_out/
-  // v7_fwd.log vs v6_fwd.log at C=250); the 4x4-plane deep layers and
-  // stride 2 measured flat-to-worse, so they stay on BK=32.
-  // OLSIM_CONV_V8 forces the two-ahead BK=32 pipeline everywhere (A/B).
-#define LAUNCH_FWD8(LG, ST) \
-  hipLaunchKernelGGL((k_conv3x3_fwd_v8<LG, ST>), grid, dim3(CONV_THREADS), \
-                     0, stream, xb, wb, yb, g)
-  if (getenv("OLSIM_CONV_V8") != nullptr) {
-    if (stride == 1) {
-      if (g.lg_ow >= 4) LAUNCH_FWD8(4, 1);
-      else if (g.lg_ow == 3) LAUNCH_FWD8(3, 1);
-      else LAUNCH_FWD8(2, 1);
-    } else {
-      if (g.lg_ow >= 4) LAUNCH_FWD8(4, 2);
-      else if (g.lg_ow == 3) LAUNCH_FWD8(3, 2);
-      else LAUNCH_FWD8(2, 2);
-    }
-    return;
+  g.tiles_m = conv3_cdiv(OC, CV6_BM);
+  g.tiles_n = conv3_cdiv(B * g.OH * g.OW, CV6_BN);
+  ConvKernel6 k = nullptr;
+  switch (conv3_route_fwd_v6(IC, OC, B, H, W, stride)) {
+    case CV3_FWD_V6_2_1: k = k_conv3x3_fwd_v6<2, 1>; break;
+    case CV3_FWD_V6_3_1: k = k_conv3x3_fwd_v6<3, 1>; break;
+    case CV3_FWD_V6_4_1: k = k_conv3x3_fwd_v6<4, 1>; break;
+    case CV3_FWD_V6_2_2: k = k_conv3x3_fwd_v6<2, 2>; break;
+    case CV3_FWD_V6_3_2: k = k_conv3x3_fwd_v6<3, 2>; break;
+    case CV3_FWD_V6_4_2: k = k_conv3x3_fwd_v6<4, 2>; break;
+    case CV3_FWD_V7_3_1: k = k_conv3x3_fwd_v7<3, 1>; break;
+    case CV3_FWD_V7_4_1: k = k_conv3x3_fwd_v7<4, 1>; break;
+    case CV3_FWD_V7_5_1: k = k_conv3x3_fwd_v7<5, 1>; break;
+    case CV3_FWD_V8_2_1: k = k_conv3x3_fwd_v8<2, 1>; break;
+    case CV3_FWD_V8_3_1: k = k_conv3x3_fwd_v8<3, 1>; break;
+    case CV3_FWD_V8_4_1: k = k_conv3x3_fwd_v8<4, 1>; break;
+    case CV3_FWD_V8_2_2: k = k_conv3x3_fwd_v8<2, 2>; break;
+    case CV3_FWD_V8_3_2: k = k_conv3x3_fwd_v8<3, 2>; break;
+    case CV3_FWD_V8_4_2: k = k_conv3x3_fwd_v8<4, 2>; break;
+    default: return;                    // not a v6-family fwd route
   }
-  const bool v7 = ((IC * 9) % 64 == 0) && stride == 1 && g.lg_ow >= 3;
-  if (stride == 1) {
-    if (v7 && g.lg_ow >= 5) LAUNCH_FWD7(5, 1);
-    else if (v7 && g.lg_ow == 4) LAUNCH_FWD7(4, 1);
-    else if (v7) LAUNCH_FWD7(3, 1);
-    else if (g.lg_ow >= 4) LAUNCH_FWD6(4, 1);
-    else if (g.lg_ow == 3) LAUNCH_FWD6(3, 1);
-    else LAUNCH_FWD6(2, 1);
-  } else {
-    if (g.lg_ow >= 4) LAUNCH_FWD6(4, 2);
-    else if (g.lg_ow == 3) LAUNCH_FWD6(3, 2);
-    else LAUNCH_FWD6(2, 2);
-  }
-#undef LAUNCH_FWD6
-#undef LAUNCH_FWD7
-#undef LAUNCH_FWD8
+  launch6(k, xp, w, y, g, stream);
+}
+
+// the four parity classes (he, we) of the stride-2 dgrad
+template <int LG>
+static inline void launch_s2(const void* dyp, const void* w, void* dx,
+                             const ConvGeom6& g, hipStream_t stream) {
+  launch6(k_conv3x3_dgrad_s2<0, 0, LG>, dyp, w, dx, g, stream);
+  launch6(k_conv3x3_dgrad_s2<0, 1, LG>, dyp, w, dx, g, stream);
+  launch6(k_conv3x3_dgrad_s2<1, 0, LG>, dyp, w, dx, g, stream);
+  launch6(k_conv3x3_dgrad_s2<1, 1, LG>, dyp, w, dx, g, stream);
 }
 
 extern "C" void ols_conv3x3_dgrad_p(const void* dyp, const void* w, void* dx,
                                     int C, int IC, int OC, int B, int H,
                                     int W, int stride, hipStream_t stream) {
-  if (stride == 1) {
-    // plane geometry: padded dy plane = H+2 x W+2 (dy is H x W at s=1);
-    // output plane = H x W
-    ConvGeom6 g;
-    fill_geom6(g, C, IC, OC, B, H, W, 1);
-    g.tiles_m = cdiv6(IC, CV6_BM);
-    g.tiles_n = cdiv6(B * H * W, CV6_BN);
-    dim3 grid(xcd_blocks6(C, g.tiles_m * g.tiles_n));
-    auto db = (const __hip_bfloat16*)dyp;
-    auto wb = (const __hip_bfloat16*)w;
-    auto xb = (__hip_bfloat16*)dx;
-    if (getenv("OLSIM_CONV_DW64") != nullptr && (OC * 9) % 64 == 0) {
-      if (g.lg_ow >= 5)
-        hipLaunchKernelGGL((k_conv3x3_dgrad_v7<5>), grid, dim3(CONV_THREADS),
-                           0, stream, db, wb, xb, g);
-      else if (g.lg_ow == 4)
-        hipLaunchKernelGGL((k_conv3x3_dgrad_v7<4>), grid, dim3(CONV_THREADS),
-                           0, stream, db, wb, xb, g);
-      else if (g.lg_ow == 3)
-        hipLaunchKernelGGL((k_conv3x3_dgrad_v7<3>), grid, dim3(CONV_THREADS),
-                           0, stream, db, wb, xb, g);
-      else
-        hipLaunchKernelGGL((k_conv3x3_dgrad_v7<2>), grid, dim3(CONV_THREADS),
-                           0, stream, db, wb, xb, g);
-      return;
-    }
-    if (g.lg_ow >= 4)
-      hipLaunchKernelGGL((k_conv3x3_dgrad_v6<4>), grid, dim3(CONV_THREADS),
-                         0, stream, db, wb, xb, g);
-    else if (g.lg_ow == 3)
-      hipLaunchKernelGGL((k_conv3x3_dgrad_v6<3>), grid, dim3(CONV_THREADS),
-                         0, stream, db, wb, xb, g);
-    else
-      hipLaunchKernelGGL((k_conv3x3_dgrad_v6<2>), grid, dim3(CONV_THREADS),
-                         0, stream, db, wb, xb, g);
-    return;
-  }
-  // stride 2: 4 parity classes; geometry carries the dy plane (OH x OW,
-  // padded Hp x Wp) and the class grid N = B*OH*OW
+  // The plane gathered from is dy's, the plane tiled over dx's (stride 1,
+  // both H x W) or one parity class of it (stride 2, OH x OW = H/2 x W/2,
+  // the size of the dy plane): either way the dy plane at stride 1.
   ConvGeom6 g;
-  int OH = H / 2, OW = W / 2;
-  g.B = B; g.Hp = OH + 2; g.Wp = OW + 2;
-  g.OH = OH; g.OW = OW;
-  g.IC = IC; g.OC = OC; g.stride = 2; g.C = C;
-  auto lg = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-  g.lg_ow = lg(OW);
-  g.lg_ohw = lg(OW) + lg(OH);
-  g.tiles_m = cdiv6(IC, CV6_BM);
-  g.tiles_n = cdiv6(B * OH * OW, CV6_BN);
-  dim3 grid(xcd_blocks6(C, g.tiles_m * g.tiles_n));
-  auto db = (const __hip_bfloat16*)dyp;
-  auto wb = (const __hip_bfloat16*)w;
-  auto xb = (__hip_bfloat16*)dx;
-#define LAUNCH_S2(HE, WE, LG) \
-  hipLaunchKernelGGL((k_conv3x3_dgrad_s2<HE, WE, LG>), grid, \
-                     dim3(CONV_THREADS), 0, stream, db, wb, xb, g)
-  if (g.lg_ow >= 4) {
-    LAUNCH_S2(0, 0, 4); LAUNCH_S2(0, 1, 4); LAUNCH_S2(1, 0, 4); LAUNCH_S2(1, 1, 4);
-  } else if (g.lg_ow == 3) {
-    LAUNCH_S2(0, 0, 3); LAUNCH_S2(0, 1, 3); LAUNCH_S2(1, 0, 3); LAUNCH_S2(1, 1, 3);
-  } else {
-    LAUNCH_S2(0, 0, 2); LAUNCH_S2(0, 1, 2); LAUNCH_S2(1, 0, 2); LAUNCH_S2(1, 1, 2);
+  fill_geom6(g, C, IC, OC, B, H / stride, W / stride, 1);
+  g.stride = stride;
+  g.tiles_m = conv3_cdiv(IC, CV6_BM);
+  g.tiles_n = conv3_cdiv(B * g.OH * g.OW, CV6_BN);
+  ConvKernel6 k = nullptr;
+  switch (conv3_route_dgrad_v6(IC, OC, B, H, W, stride)) {
+    case CV3_DGRAD_V6_2: k = k_conv3x3_dgrad_v6<2>; break;
+    case CV3_DGRAD_V6_3: k = k_conv3x3_dgrad_v6<3>; break;
+    case CV3_DGRAD_V6_4: k = k_conv3x3_dgrad_v6<4>; break;
+    case CV3_DGRAD_V7_2: k = k_conv3x3_dgrad_v7<2>; break;
+    case CV3_DGRAD_V7_3: k = k_conv3x3_dgrad_v7<3>; break;
+    case CV3_DGRAD_V7_4: k = k_conv3x3_dgrad_v7<4>; break;
+    case CV3_DGRAD_V7_5: k = k_conv3x3_dgrad_v7<5>; break;
+    case CV3_DGRAD_S2_2: launch_s2<2>(dyp, w, dx, g, stream); return;
+    case CV3_DGRAD_S2_3: launch_s2<3>(dyp, w, dx, g, stream); return;
+    case CV3_DGRAD_S2_4: launch_s2<4>(dyp, w, dx, g, stream); return;
+    default: return;                    // not a v6-family dgrad route
   }
-#undef LAUNCH_S2
+  launch6(k, dyp, w, dx, g, stream);
 }
 
 extern "C" void ols_conv3x3_wgrad_p(const void* xp, const void* dy, void* dw,
@@ -1489,31 +1437,15 @@ extern "C" void ols_conv3x3_wgrad_p(const void* xp, const void* dy, void* dw,
                                     int W, int stride, hipStream_t stream) {
   ConvGeom6 g;
   fill_geom6(g, C, IC, OC, B, H, W, stride);
-  g.tiles_m = cdiv6(OC, CV6_BM);
-  g.tiles_n = cdiv6(IC * 9, CV6_BN);
-  dim3 grid(xcd_blocks6(C, g.tiles_m * g.tiles_n));
-  const int NN = B * g.OH * g.OW;
-  if (stride == 2 && g.OW >= 8 && getenv("OLSIM_CONV_DW8") == nullptr) {
-    hipLaunchKernelGGL(k_conv3x3_wgrad_v8s, grid, dim3(CONV_THREADS), 0,
-                       stream, (const __hip_bfloat16*)xp,
-                       (const __hip_bfloat16*)dy, (__hip_bfloat16*)dw, g);
-    return;
+  g.tiles_m = conv3_cdiv(OC, CV6_BM);
+  g.tiles_n = conv3_cdiv(IC * 9, CV6_BN);
+  ConvKernel6 k = nullptr;
+  switch (conv3_route_wgrad_v6(IC, OC, B, H, W, stride)) {
+    case CV3_WGRAD_V6: k = k_conv3x3_wgrad_v6; break;
+    case CV3_WGRAD_V7: k = k_conv3x3_wgrad_v7; break;
+    case CV3_WGRAD_V8: k = k_conv3x3_wgrad_v8; break;
+    case CV3_WGRAD_V8S: k = k_conv3x3_wgrad_v8s; break;
+    default: return;                    // not a v6-family wgrad route
   }
-  if (stride == 1 && g.OW >= 8 && getenv("OLSIM_CONV_DW8") == nullptr) {
-    // run-vectorised producer (v8): 8 consecutive stride-1 q stay in
-    // one padded row; OLSIM_CONV_DW8=0 restores the scalar gather
-    hipLaunchKernelGGL(k_conv3x3_wgrad_v8, grid, dim3(CONV_THREADS), 0,
-                       stream, (const __hip_bfloat16*)xp,
-                       (const __hip_bfloat16*)dy, (__hip_bfloat16*)dw, g);
-    return;
-  }
-  if (getenv("OLSIM_CONV_DW64") != nullptr && NN % 64 == 0) {
-    hipLaunchKernelGGL(k_conv3x3_wgrad_v7, grid, dim3(CONV_THREADS), 0,
-                       stream, (const __hip_bfloat16*)xp,
-                       (const __hip_bfloat16*)dy, (__hip_bfloat16*)dw, g);
-    return;
-  }
-  hipLaunchKernelGGL(k_conv3x3_wgrad_v6, grid, dim3(CONV_THREADS), 0, stream,
-                     (const __hip_bfloat16*)xp, (const __hip_bfloat16*)dy,
-                     (__hip_bfloat16*)dw, g);
+  launch6(k, xp, dy, dw, g, stream);
 }

@@ -1,0 +1,195 @@
+// Which conv3x3 kernel, with which template arguments, a shape runs.
+// One function per family and direction; the launchers in client_conv.hip
+// and client_conv2.hip switch on the result and the binding's
+// conv3x3_route() reports its name, so a test can assert the kernel a
+// shape reaches.  Plain C++ on ints: no HIP types, compiles on any host.
+#pragma once
+
+#include <cstdlib>
+#include <cstring>
+
+// name<template arguments> as conv3x3_route() spells it.  fwd_v6/v7/v8
+// carry <LG_OW, STRIDE>, dgrad_v6/v7 <LG_OW>, dgrad_s2 <LG_OW> (its four
+// parity-class launches share it), fwd_v5 <ROW_HOIST>, dgrad_v5 <STRIDE>.
+#define CONV3_ROUTES(X)                                                     \
+  X(FWD_V2, "fwd_v2")                                                       \
+  X(FWD_V5_TRUE, "fwd_v5<true>") X(FWD_V5_FALSE, "fwd_v5<false>")           \
+  X(DGRAD_GENERIC, "dgrad_generic")                                         \
+  X(DGRAD_V5_1, "dgrad_v5<1>") X(DGRAD_V5_2, "dgrad_v5<2>")                 \
+  X(WGRAD_GENERIC, "wgrad_generic") X(WGRAD_V5, "wgrad_v5")                 \
+  X(FWD_V6_2_1, "fwd_v6<2,1>") X(FWD_V6_3_1, "fwd_v6<3,1>")                 \
+  X(FWD_V6_4_1, "fwd_v6<4,1>") X(FWD_V6_2_2, "fwd_v6<2,2>")                 \
+  X(FWD_V6_3_2, "fwd_v6<3,2>") X(FWD_V6_4_2, "fwd_v6<4,2>")                 \
+  X(FWD_V7_3_1, "fwd_v7<3,1>") X(FWD_V7_4_1, "fwd_v7<4,1>")                 \
+  X(FWD_V7_5_1, "fwd_v7<5,1>")                                              \
+  X(FWD_V8_2_1, "fwd_v8<2,1>") X(FWD_V8_3_1, "fwd_v8<3,1>")                 \
+  X(FWD_V8_4_1, "fwd_v8<4,1>") X(FWD_V8_2_2, "fwd_v8<2,2>")                 \
+  X(FWD_V8_3_2, "fwd_v8<3,2>") X(FWD_V8_4_2, "fwd_v8<4,2>")                 \
+  X(DGRAD_V6_2, "dgrad_v6<2>") X(DGRAD_V6_3, "dgrad_v6<3>")                 \
+  X(DGRAD_V6_4, "dgrad_v6<4>")                                              \
+  X(DGRAD_V7_2, "dgrad_v7<2>") X(DGRAD_V7_3, "dgrad_v7<3>")                 \
+  X(DGRAD_V7_4, "dgrad_v7<4>") X(DGRAD_V7_5, "dgrad_v7<5>")                 \
+  X(DGRAD_S2_2, "dgrad_s2<2>") X(DGRAD_S2_3, "dgrad_s2<3>")                 \
+  X(DGRAD_S2_4, "dgrad_s2<4>")                                              \
+  X(WGRAD_V6, "wgrad_v6") X(WGRAD_V7, "wgrad_v7")                           \
+  X(WGRAD_V8, "wgrad_v8") X(WGRAD_V8S, "wgrad_v8s")
+
+enum Conv3Route {
+#define X(id, name) CV3_##id,
+  CONV3_ROUTES(X)
+#undef X
+};
+
+static inline const char* conv3_route_name(Conv3Route r) {
+  static const char* const names[] = {
+#define X(id, name) name,
+      CONV3_ROUTES(X)
+#undef X
+  };
+  return names[r];
+}
+
+// The four A/B switches, read on every call.  OLSIM_CONV_V=5 sends every
+// shape to the v5 family; the other three act on presence, whatever the
+// value (OLSIM_CONV_DW8=0 restores the scalar wgrad gather because it is
+// set): OLSIM_CONV_V8 the two-ahead fwd_v8, OLSIM_CONV_DW64 the BK=64
+// dgrad_v7 / wgrad_v7, OLSIM_CONV_DW8 no run-vectorised wgrad_v8 / v8s.
+struct Conv3Env {
+  bool v5, v8, dw64, no_dw8;
+};
+
+static inline Conv3Env conv3_env() {
+  const char* v = getenv("OLSIM_CONV_V");
+  return {v != nullptr && strcmp(v, "5") == 0,
+          getenv("OLSIM_CONV_V8") != nullptr,
+          getenv("OLSIM_CONV_DW64") != nullptr,
+          getenv("OLSIM_CONV_DW8") != nullptr};
+}
+
+static inline int conv3_cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline bool conv3_is_p2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+static inline int conv3_lg(int v) {
+  int l = 0;
+  while ((1 << l) < v) ++l;
+  return l;
+}
+// LG_OW template argument of a kernel instantiated for lo..hi
+static inline int conv3_clamp(int v, int lo, int hi) {
+  return v < lo ? lo : v > hi ? hi : v;
+}
+
+// ---- v5 family (client_conv.hip): any shape, dense operands ---------------
+
+static inline Conv3Route conv3_route_fwd_v5(int IC, int OC, int B, int H,
+                                            int W, int stride) {
+  const int OH = conv3_cdiv(H, stride), OW = conv3_cdiv(W, stride);
+  const bool v5_ok = conv3_is_p2(OW) && conv3_is_p2(OH) && (IC * 9) % 32 == 0;
+  if (!v5_ok) return CV3_FWD_V2;
+  // ROW_HOIST: a 16-column segment lies inside one output row
+  return OW >= 16 ? CV3_FWD_V5_TRUE : CV3_FWD_V5_FALSE;
+}
+
+static inline Conv3Route conv3_route_dgrad_v5(int IC, int OC, int B, int H,
+                                              int W, int stride) {
+  const int OH = conv3_cdiv(H, stride), OW = conv3_cdiv(W, stride);
+  // dgrad_v5 decomposes n with log2(W) = log2(OW * stride) and H == W:
+  // an odd plane at stride 2 (OH = ceil(H/2)) takes the generic kernel
+  const bool v5_ok = conv3_is_p2(OW) && conv3_is_p2(OH) && (OC * 9) % 32 == 0
+                     && (stride == 1 || stride == 2) && H == W
+                     && H == OH * stride;
+  if (!v5_ok) return CV3_DGRAD_GENERIC;
+  return stride == 1 ? CV3_DGRAD_V5_1 : CV3_DGRAD_V5_2;
+}
+
+static inline Conv3Route conv3_route_wgrad_v5(int IC, int OC, int B, int H,
+                                              int W, int stride) {
+  const int OH = conv3_cdiv(H, stride), OW = conv3_cdiv(W, stride);
+  const bool v5_ok = conv3_is_p2(OW) && conv3_is_p2(OH)
+                     && (B * OH * OW) % 32 == 0;
+  return v5_ok ? CV3_WGRAD_V5 : CV3_WGRAD_GENERIC;
+}
+
+// ---- v6 family (client_conv2.hip): padded operands ------------------------
+
+// true when the v6 padded path supports the shape (pow2 planes, K%32==0)
+static inline bool conv3_v6_ok(int IC, int OC, int B, int H, int W,
+                               int stride) {
+  const int OH = conv3_cdiv(H, stride), OW = conv3_cdiv(W, stride);
+  if (!conv3_is_p2(OH) || !conv3_is_p2(OW) || OW < 4) return false;
+  // stride-2 dgrad scatters into a 2*OH x 2*OW dX plane: odd H or W
+  // (7 -> 4) would index dy_pad and dx with the wrong plane sizes
+  if (stride == 2 && ((H | W) & 1)) return false;
+  if ((IC * 9) % 32 != 0) return false;             // fwd K
+  if ((OC * 9) % 32 != 0) return false;             // dgrad K (s=1)
+  if (stride == 2 && OC % 32 != 0) return false;    // smallest s2 class K=OC
+  if (stride != 1 && stride != 2) return false;
+  if ((B * OH * OW) % 32 != 0) return false;        // wgrad A-direct rows
+  return true;
+}
+
+// The shapes below passed conv3_v6_ok: stride is 1 or 2, planes are pow2.
+
+static inline Conv3Route conv3_route_fwd_v6(int IC, int OC, int B, int H,
+                                            int W, int stride) {
+  static const Conv3Route v6[2][3] = {
+      {CV3_FWD_V6_2_1, CV3_FWD_V6_3_1, CV3_FWD_V6_4_1},
+      {CV3_FWD_V6_2_2, CV3_FWD_V6_3_2, CV3_FWD_V6_4_2}};
+  static const Conv3Route v7[3] = {CV3_FWD_V7_3_1, CV3_FWD_V7_4_1,
+                                   CV3_FWD_V7_5_1};
+  static const Conv3Route v8[2][3] = {
+      {CV3_FWD_V8_2_1, CV3_FWD_V8_3_1, CV3_FWD_V8_4_1},
+      {CV3_FWD_V8_2_2, CV3_FWD_V8_3_2, CV3_FWD_V8_4_2}};
+  const int lg_ow = conv3_lg(conv3_cdiv(W, stride));
+  // OLSIM_CONV_V8 forces the two-ahead BK=32 pipeline everywhere (A/B)
+  if (conv3_env().v8) return v8[stride != 1][conv3_clamp(lg_ow, 2, 4) - 2];
+  // BK=64 (v7) wins +5..10% at OW >= 8 stride 1 (A/B at C=250); the
+  // 4x4-plane deep layers and stride 2 measured flat-to-worse, so they
+  // stay on BK=32.
+  if ((IC * 9) % 64 == 0 && stride == 1 && lg_ow >= 3)
+    return v7[conv3_clamp(lg_ow, 3, 5) - 3];
+  return v6[stride != 1][conv3_clamp(lg_ow, 2, 4) - 2];
+}
+
+static inline Conv3Route conv3_route_dgrad_v6(int IC, int OC, int B, int H,
+                                              int W, int stride) {
+  static const Conv3Route v6[3] = {CV3_DGRAD_V6_2, CV3_DGRAD_V6_3,
+                                   CV3_DGRAD_V6_4};
+  static const Conv3Route v7[4] = {CV3_DGRAD_V7_2, CV3_DGRAD_V7_3,
+                                   CV3_DGRAD_V7_4, CV3_DGRAD_V7_5};
+  static const Conv3Route s2[3] = {CV3_DGRAD_S2_2, CV3_DGRAD_S2_3,
+                                   CV3_DGRAD_S2_4};
+  const int lg_ow = conv3_lg(conv3_cdiv(W, stride));
+  // stride 2: four parity classes, each a dense GEMM over the dy plane
+  if (stride != 1) return s2[conv3_clamp(lg_ow, 2, 4) - 2];
+  if (conv3_env().dw64 && (OC * 9) % 64 == 0)
+    return v7[conv3_clamp(lg_ow, 2, 5) - 2];
+  return v6[conv3_clamp(lg_ow, 2, 4) - 2];
+}
+
+static inline Conv3Route conv3_route_wgrad_v6(int IC, int OC, int B, int H,
+                                              int W, int stride) {
+  const int OH = conv3_cdiv(H, stride), OW = conv3_cdiv(W, stride);
+  const Conv3Env env = conv3_env();
+  // run-vectorised producer (v8 / v8s): 8 consecutive q stay in one
+  // padded row; OLSIM_CONV_DW8 restores the scalar gather
+  if (OW >= 8 && !env.no_dw8)
+    return stride == 1 ? CV3_WGRAD_V8 : CV3_WGRAD_V8S;
+  if (env.dw64 && (B * OH * OW) % 64 == 0) return CV3_WGRAD_V7;
+  return CV3_WGRAD_V6;
+}
+
+// dir: 0 fwd, 1 dgrad, 2 wgrad.  Includes the family decision the Python
+// dispatcher makes (ops/conv.py _v6_ok): v6 unless OLSIM_CONV_V=5 or the
+// shape is outside conv3_v6_ok.
+static inline Conv3Route conv3_route(int dir, int IC, int OC, int B, int H,
+                                     int W, int stride) {
+  const bool v6 = !conv3_env().v5 && conv3_v6_ok(IC, OC, B, H, W, stride);
+  if (dir == 0)
+    return v6 ? conv3_route_fwd_v6(IC, OC, B, H, W, stride)
+              : conv3_route_fwd_v5(IC, OC, B, H, W, stride);
+  if (dir == 1)
+    return v6 ? conv3_route_dgrad_v6(IC, OC, B, H, W, stride)
+              : conv3_route_dgrad_v5(IC, OC, B, H, W, stride);
+  return v6 ? conv3_route_wgrad_v6(IC, OC, B, H, W, stride)
+            : conv3_route_wgrad_v5(IC, OC, B, H, W, stride);
+}

@@ -9,6 +9,7 @@
 // cross-wave combine, (2) write dlogits.  bf16/f32 in, fp32 math.
 
 #include "common.h"
+#include "ols_ops.h"
 
 template <typename T>
 __global__ __launch_bounds__(OLS_THREADS) void k_ce_fwd_bwd(

@@ -16,6 +16,7 @@
 // streaming saxpy: 3 streams (read w, read g, write w) -> HBM-bound.
 
 #include "common.h"
+#include "ols_ops.h"
 
 template <typename T, int V>
 __global__ __launch_bounds__(OLS_THREADS) void k_sgd_plain(

@@ -31,7 +31,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "groupnorm.h"
+#include "ols_ops.h"
 
 typedef __hip_bfloat16 bf16;
 

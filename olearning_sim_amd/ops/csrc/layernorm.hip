@@ -12,6 +12,7 @@
 // with c = row / rows_per_client.
 
 #include "common.h"
+#include "ols_ops.h"
 
 #define LN_ROWS 4              // rows (waves) per workgroup
 

@@ -14,6 +14,7 @@
 // Requires W % 2 == 0 (the wrapper falls back to F.pad otherwise).
 
 #include "common.h"
+#include "ols_ops.h"
 
 template <typename T>
 __global__ __launch_bounds__(OLS_THREADS) void k_pad2d(

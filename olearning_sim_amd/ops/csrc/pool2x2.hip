@@ -11,6 +11,7 @@
 // even.
 
 #include "common.h"
+#include "ols_ops.h"
 
 template <typename T>
 __global__ __launch_bounds__(OLS_THREADS) void k_pool2x2_fwd(

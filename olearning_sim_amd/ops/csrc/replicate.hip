@@ -15,6 +15,7 @@
 // the Python wrappers fall back to composed torch ops otherwise.
 
 #include "common.h"
+#include "ols_ops.h"
 
 template <typename T>
 __global__ __launch_bounds__(OLS_THREADS) void k_replicate(

@@ -7,6 +7,7 @@
 // reads AND writes, padded LDS rows; edge tiles take the scalar path.
 
 #include "common.h"
+#include "ols_ops.h"
 
 #define TR_TILE 64
 #define TR_PAD 8           // shorts; keeps write-side b128 reads off one bank

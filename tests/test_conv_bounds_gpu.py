@@ -1,8 +1,9 @@
 """conv3x3 (every kernel family and dispatch branch), conv5x5 and the
 2x2 max-pool against fp64 references with the derived bounds of
 tests/kernel_bounds.py.  Each conv3x3 case asserts the family the
-dispatcher takes and each conv5x5 case the route of all three
-directions, so a silent change of route fails here."""
+dispatcher takes and the kernel, with its template arguments, of all
+three directions; each conv5x5 case the route of all three directions.
+A silent change of route or of a threshold inside a family fails here."""
 
 import pytest
 import torch
@@ -39,16 +40,21 @@ def _conv3_case(shape):
     return _REF_CACHE[shape]
 
 
-def _check_conv3x3(shape, v6, tag, forced_v5=False):
-    """forced_v5: OLSIM_CONV_V=5 is set, which ops.conv3x3_v6_ok (the
-    shape predicate) ignores; the dispatcher's own _v6_ok must then say
-    v5 for a shape of the v6 family."""
+def _check_conv3x3(shape, v6, tag, routes, forced_v5=False):
+    """routes: the (fwd, dgrad, wgrad) kernels, as ops.conv3x3_route
+    spells them, that the shape reaches under the environment the caller
+    has set.  forced_v5: OLSIM_CONV_V=5 is set, which ops.conv3x3_v6_ok
+    (the shape predicate) ignores; the dispatcher's own _v6_ok must then
+    say v5 for a shape of the v6 family."""
     from olearning_sim_amd.ops.conv import client_conv3x3, _v6_ok
     from olearning_sim_amd.ops.fused import load_hip_ops
     ops = load_hip_ops(required=True)
     C, IC, OC, B, H, W, s = shape
     assert bool(ops.conv3x3_v6_ok(IC, OC, B, H, W, s)) == v6, \
         f"{shape}: expected the {'v6' if v6 else 'v5'} family"
+    got = tuple(ops.conv3x3_route(d, IC, OC, B, H, W, s)
+                for d in ("fwd", "dgrad", "wgrad"))
+    assert got == tuple(routes), f"{shape}: routes {got}, expected {routes}"
     x, w, dy, ref = _conv3_case(shape)
     xg = x.cuda().requires_grad_(True)
     wg = w.cuda().requires_grad_(True)
@@ -65,50 +71,118 @@ def _check_conv3x3(shape, v6, tag, forced_v5=False):
                    label=tag + ".wgrad")
 
 
-# (C, IC, OC, B, H, W, stride) -> takes the v6 padded family?
-V6_SHAPES = [
-    (1, 64, 64, 1, 32, 32, 1),     # fwd_v7<5>: the benchmark's stage 0
-    (2, 64, 64, 2, 8, 16, 1),      # non-square planes
-    (2, 64, 64, 2, 16, 8, 1),
-    (2, 64, 64, 2, 4, 32, 1),
-    (2, 64, 128, 2, 16, 32, 2),    # stride-2 parity classes, 8x16 dy plane
-    (2, 64, 96, 2, 4, 4, 1),       # OC tile tail; B*OH*OW = 32 < one N tile
-    (2, 32, 32, 2, 4, 4, 1),       # half M tile, K = 288
-    (2, 64, 64, 4, 4, 4, 1),       # OW = 4, B*OH*OW = 64 (wgrad_v7 under DW64)
-    (2, 64, 128, 4, 8, 8, 2),      # stride 2 at OW = 4
-]
-V5_SHAPES = [
-    (2, 64, 64, 4, 8, 4, 2),       # OW = 2 < 4: below the v6 floor
-    (2, 8, 24, 3, 6, 10, 1),       # generic kernels: no pow2 plane
-    (2, 16, 16, 2, 8, 16, 1),      # fwd_v2 (K % 32 != 0) + wgrad_v5
-    (1, 3, 8, 2, 7, 9, 2),         # odd, non-pow2, stride 2
+# The expected routes below were read off the launchers' branches by hand
+# (fwd_v6/v7/v8<LG_OW,STRIDE>, dgrad_v6/v7/s2<LG_OW> with LG_OW = log2(OW)
+# clamped to the instantiated range), not produced by conv3x3_route.
+
+# (C, IC, OC, B, H, W, stride) of the v6 padded family -> (fwd, dgrad,
+# wgrad) with no variable set
+V6_ROUTES = {
+    # the benchmark's stage 0
+    (1, 64, 64, 1, 32, 32, 1): ("fwd_v7<5,1>", "dgrad_v6<4>", "wgrad_v8"),
+    # non-square planes
+    (2, 64, 64, 2, 8, 16, 1): ("fwd_v7<4,1>", "dgrad_v6<4>", "wgrad_v8"),
+    (2, 64, 64, 2, 16, 8, 1): ("fwd_v7<3,1>", "dgrad_v6<3>", "wgrad_v8"),
+    (2, 64, 64, 2, 4, 32, 1): ("fwd_v7<5,1>", "dgrad_v6<4>", "wgrad_v8"),
+    # stride-2 parity classes, 8x16 dy plane
+    (2, 64, 128, 2, 16, 32, 2): ("fwd_v6<4,2>", "dgrad_s2<4>", "wgrad_v8s"),
+    # OC tile tail; B*OH*OW = 32 < one N tile
+    (2, 64, 96, 2, 4, 4, 1): ("fwd_v6<2,1>", "dgrad_v6<2>", "wgrad_v6"),
+    # half M tile; K = 288 is no multiple of 64, so no BK=64 kernel
+    (2, 32, 32, 2, 4, 4, 1): ("fwd_v6<2,1>", "dgrad_v6<2>", "wgrad_v6"),
+    # OW = 4, B*OH*OW = 64 (dgrad_v7<2> and wgrad_v7 under DW64)
+    (2, 64, 64, 4, 4, 4, 1): ("fwd_v6<2,1>", "dgrad_v6<2>", "wgrad_v6"),
+    # stride 2 at OW = 4
+    (2, 64, 128, 4, 8, 8, 2): ("fwd_v6<2,2>", "dgrad_s2<2>", "wgrad_v6"),
+    # stride 2 at OW = 8: the <3,2> forward kernels and dgrad_s2<3>
+    (2, 64, 128, 2, 16, 16, 2): ("fwd_v6<3,2>", "dgrad_s2<3>", "wgrad_v8s"),
+    # K = 288 at OW = 8 and 16: the BK=32 forward where v7 would run
+    (2, 32, 32, 1, 8, 8, 1): ("fwd_v6<3,1>", "dgrad_v6<3>", "wgrad_v8"),
+    (2, 32, 32, 1, 16, 16, 1): ("fwd_v6<4,1>", "dgrad_v6<4>", "wgrad_v8"),
+}
+V6_SHAPES = list(V6_ROUTES)
+
+# what a variable changes in V6_ROUTES.  OLSIM_CONV_V8: every forward is
+# fwd_v8, LG_OW clamped to 2..4, before v7 is considered.
+V8_FWD = {
+    (1, 64, 64, 1, 32, 32, 1): "fwd_v8<4,1>",
+    (2, 64, 64, 2, 8, 16, 1): "fwd_v8<4,1>",
+    (2, 64, 64, 2, 16, 8, 1): "fwd_v8<3,1>",
+    (2, 64, 64, 2, 4, 32, 1): "fwd_v8<4,1>",
+    (2, 64, 128, 2, 16, 32, 2): "fwd_v8<4,2>",
+    (2, 64, 96, 2, 4, 4, 1): "fwd_v8<2,1>",
+    (2, 32, 32, 2, 4, 4, 1): "fwd_v8<2,1>",
+    (2, 64, 64, 4, 4, 4, 1): "fwd_v8<2,1>",
+    (2, 64, 128, 4, 8, 8, 2): "fwd_v8<2,2>",
+    (2, 64, 128, 2, 16, 16, 2): "fwd_v8<3,2>",
+    (2, 32, 32, 1, 8, 8, 1): "fwd_v8<3,1>",
+    (2, 32, 32, 1, 16, 16, 1): "fwd_v8<4,1>",
+}
+# OLSIM_CONV_DW64: dgrad_v7 at stride 1 when OC*9 % 64 == 0 (OC = 96 and
+# 32 are not), LG_OW up to 5; wgrad_v7 when v8 / v8s do not run (OW < 8)
+# and B*OH*OW % 64 == 0.  Shapes not listed keep their V6_ROUTES entry.
+DW64_DGRAD_WGRAD = {
+    (1, 64, 64, 1, 32, 32, 1): ("dgrad_v7<5>", "wgrad_v8"),
+    (2, 64, 64, 2, 8, 16, 1): ("dgrad_v7<4>", "wgrad_v8"),
+    (2, 64, 64, 2, 16, 8, 1): ("dgrad_v7<3>", "wgrad_v8"),
+    (2, 64, 64, 2, 4, 32, 1): ("dgrad_v7<5>", "wgrad_v8"),
+    (2, 64, 64, 4, 4, 4, 1): ("dgrad_v7<2>", "wgrad_v7"),
+    (2, 64, 128, 4, 8, 8, 2): ("dgrad_s2<2>", "wgrad_v7"),
+}
+
+# shapes outside the v6 family
+V5_ROUTES = {
+    # OW = 2 < 4: below the v6 floor; H != W
+    (2, 64, 64, 4, 8, 4, 2): ("fwd_v5<false>", "dgrad_generic", "wgrad_v5"),
+    # no pow2 plane
+    (2, 8, 24, 3, 6, 10, 1): ("fwd_v2", "dgrad_generic", "wgrad_generic"),
+    # K = 144 is no multiple of 32 in fwd and dgrad
+    (2, 16, 16, 2, 8, 16, 1): ("fwd_v2", "dgrad_generic", "wgrad_v5"),
+    # odd, non-pow2, stride 2
+    (1, 3, 8, 2, 7, 9, 2): ("fwd_v2", "dgrad_generic", "wgrad_generic"),
     # odd planes at stride 2 (7 -> 4): v6 and dgrad_v5 assume H = 2*OH
-    (2, 64, 64, 2, 7, 7, 2),
-    (2, 64, 64, 2, 7, 8, 2),
-    (1, 3, 64, 1, 32, 32, 1),      # IC = 3 stem: fwd_v2 + dgrad_v5, stride 1
+    (2, 64, 64, 2, 7, 7, 2): ("fwd_v5<false>", "dgrad_generic", "wgrad_v5"),
+    (2, 64, 64, 2, 7, 8, 2): ("fwd_v5<false>", "dgrad_generic", "wgrad_v5"),
+    # IC = 3 stem, stride 1
+    (1, 3, 64, 1, 32, 32, 1): ("fwd_v2", "dgrad_v5<1>", "wgrad_v5"),
+}
+V5_SHAPES = list(V5_ROUTES)
+
+# v6-family shapes run under OLSIM_CONV_V=5: fwd_v5<true> (OW >= 16) and
+# <false>, dgrad_v5 at stride 1 and stride 2
+FORCED_V5_ROUTES = {
+    (1, 64, 64, 1, 32, 32, 1): ("fwd_v5<true>", "dgrad_v5<1>", "wgrad_v5"),
+    (2, 64, 128, 2, 16, 16, 2): ("fwd_v5<false>", "dgrad_v5<2>", "wgrad_v5"),
+}
+FORCED_V5_SHAPES = list(FORCED_V5_ROUTES)
+
+# OLSIM_CONV_DW8 (set, whatever its value) at OW >= 8: no wgrad_v8 / v8s
+DW8_SHAPES = [
+    (2, 64, 64, 2, 16, 8, 1),
+    (2, 64, 128, 2, 16, 32, 2),
 ]
-# v6-family shapes run under OLSIM_CONV_V=5: fwd_v5<true> and dgrad_v5 at
-# stride 1 and stride 2
-FORCED_V5_SHAPES = [
-    (1, 64, 64, 1, 32, 32, 1),
-    (2, 64, 128, 2, 16, 16, 2),
-]
+
+CONV3_VARS = ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
+              "OLSIM_CONV_DW8")
+
+
+def _conv3_env(monkeypatch, var=None, value="1"):
+    for other in CONV3_VARS:
+        monkeypatch.delenv(other, raising=False)
+    if var is not None:
+        monkeypatch.setenv(var, value)
 
 
 @pytest.mark.parametrize("shape", V6_SHAPES, ids=str)
 def test_conv3x3_v6_family_bounded(shape, monkeypatch):
-    for var in ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
-                "OLSIM_CONV_DW8"):
-        monkeypatch.delenv(var, raising=False)
-    _check_conv3x3(shape, True, "conv3.v6")
+    _conv3_env(monkeypatch)
+    _check_conv3x3(shape, True, "conv3.v6", V6_ROUTES[shape])
 
 
 @pytest.mark.parametrize("shape", V5_SHAPES, ids=str)
 def test_conv3x3_v5_family_bounded(shape, monkeypatch):
-    for var in ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
-                "OLSIM_CONV_DW8"):
-        monkeypatch.delenv(var, raising=False)
-    _check_conv3x3(shape, False, "conv3.v5")
+    _conv3_env(monkeypatch)
+    _check_conv3x3(shape, False, "conv3.v5", V5_ROUTES[shape])
 
 
 @pytest.mark.parametrize("var", ["OLSIM_CONV_V8", "OLSIM_CONV_DW64"])
@@ -116,11 +190,24 @@ def test_conv3x3_v5_family_bounded(shape, monkeypatch):
 def test_conv3x3_env_gated_kernels_bounded(shape, var, monkeypatch):
     """fwd_v8 (OLSIM_CONV_V8) and dgrad_v7 / wgrad_v7 (OLSIM_CONV_DW64);
     the launchers read the environment on every call."""
-    for other in ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
-                  "OLSIM_CONV_DW8"):
-        monkeypatch.delenv(other, raising=False)
-    monkeypatch.setenv(var, "1")
-    _check_conv3x3(shape, True, "conv3." + var.rsplit("_", 1)[1].lower())
+    _conv3_env(monkeypatch, var)
+    fwd, dgrad, wgrad = V6_ROUTES[shape]
+    if var == "OLSIM_CONV_V8":
+        fwd = V8_FWD[shape]
+    else:
+        dgrad, wgrad = DW64_DGRAD_WGRAD.get(shape, (dgrad, wgrad))
+    _check_conv3x3(shape, True, "conv3." + var.rsplit("_", 1)[1].lower(),
+                   (fwd, dgrad, wgrad))
+
+
+@pytest.mark.parametrize("shape", DW8_SHAPES, ids=str)
+def test_conv3x3_dw8_restores_scalar_wgrad(shape, monkeypatch):
+    """OLSIM_CONV_DW8=0 acts because it is set: wgrad_v6 where wgrad_v8
+    (stride 1) and wgrad_v8s (stride 2) run by default."""
+    _conv3_env(monkeypatch, "OLSIM_CONV_DW8", "0")
+    fwd, dgrad, wgrad = V6_ROUTES[shape]
+    assert wgrad in ("wgrad_v8", "wgrad_v8s")
+    _check_conv3x3(shape, True, "conv3.dw8", (fwd, dgrad, "wgrad_v6"))
 
 
 @pytest.mark.parametrize("shape", FORCED_V5_SHAPES, ids=str)
@@ -128,10 +215,9 @@ def test_conv3x3_forced_v5_kernels_bounded(shape, monkeypatch):
     """The pipelined v5 kernels a v6-family shape gets under
     OLSIM_CONV_V=5 (the A/B switch).  The family assertion goes through
     the dispatcher's _v6_ok, which reads the variable."""
-    for other in ("OLSIM_CONV_V8", "OLSIM_CONV_DW64", "OLSIM_CONV_DW8"):
-        monkeypatch.delenv(other, raising=False)
-    monkeypatch.setenv("OLSIM_CONV_V", "5")
-    _check_conv3x3(shape, True, "conv3.forced_v5", forced_v5=True)
+    _conv3_env(monkeypatch, "OLSIM_CONV_V", "5")
+    _check_conv3x3(shape, True, "conv3.forced_v5", FORCED_V5_ROUTES[shape],
+                   forced_v5=True)
 
 
 # ---------------------------------------------------------------------------

@@ -440,3 +440,117 @@ def test_layernorm_matches_torch(shape):
                                atol=0.3, rtol=5e-2)
     torch.testing.assert_close(bg.grad.float().cpu(), br.grad,
                                atol=0.3, rtol=5e-2)
+
+
+# ---------------------------------------------------------------------------
+# conv wrappers: operand checks.  Every bad call below must raise from the
+# binding's host-side checks, before any kernel is launched; the good call
+# first shows that the shapes the bad ones deviate from are accepted.
+
+def _bf16(*shape):
+    return torch.zeros(*shape, dtype=torch.bfloat16, device="cuda")
+
+
+def _rejects(fn, *args, match):
+    with pytest.raises(RuntimeError, match=match):
+        fn(*args)
+
+
+def test_conv3x3_v5_wrappers_reject_mismatched_operands():
+    from olearning_sim_amd.ops import load_hip_ops
+    ops = load_hip_ops(required=True)
+    C, IC, OC, B, H, W = 2, 2, 3, 1, 4, 4
+    x, w, dy = _bf16(C, IC, B, H, W), _bf16(C, OC, IC, 3, 3), \
+        _bf16(C, OC, B, H, W)
+    assert ops.conv3x3_fwd(x, w, 1).shape == dy.shape
+    assert ops.conv3x3_dgrad(dy, w, H, W, 1).shape == x.shape
+    assert ops.conv3x3_wgrad(x, dy, 1).shape == w.shape
+    m = "conv3x3"
+    # wrong dtype on the second operand
+    _rejects(ops.conv3x3_fwd, x, w.float(), 1, match=m)
+    _rejects(ops.conv3x3_dgrad, dy, w.float(), H, W, 1, match=m)
+    _rejects(ops.conv3x3_wgrad, x, dy.float(), 1, match=m)
+    # dy with the wrong OC, the wrong B, the wrong plane
+    _rejects(ops.conv3x3_dgrad, _bf16(C, OC + 1, B, H, W), w, H, W, 1,
+             match=m)
+    _rejects(ops.conv3x3_wgrad, x, _bf16(C, OC, B + 1, H, W), 1, match=m)
+    _rejects(ops.conv3x3_dgrad, _bf16(C, OC, B, H, W - 1), w, H, W, 1,
+             match=m)
+    _rejects(ops.conv3x3_wgrad, x, _bf16(C, OC, B, H // 2, W), 1, match=m)
+    _rejects(ops.conv3x3_wgrad, x, dy, 2, match=m)      # dy is H x W, not H/2
+    # w with the wrong C, the wrong IC, not 3x3; a non-contiguous w
+    _rejects(ops.conv3x3_fwd, x, _bf16(C + 1, OC, IC, 3, 3), 1, match=m)
+    _rejects(ops.conv3x3_dgrad, dy, _bf16(C + 1, OC, IC, 3, 3), H, W, 1,
+             match=m)
+    _rejects(ops.conv3x3_fwd, x, _bf16(C, OC, IC + 1, 3, 3), 1, match=m)
+    _rejects(ops.conv3x3_fwd, x, _bf16(C, OC, IC, 5, 5), 1, match=m)
+    _rejects(ops.conv3x3_dgrad, dy, _bf16(C, IC, OC, 3, 3).transpose(1, 2),
+             H, W, 1, match=m)
+    _rejects(ops.conv3x3_fwd, x, w, 3, match=m)         # stride
+    torch.cuda.synchronize()
+
+
+def test_conv3x3_v6_wrappers_reject_mismatched_operands():
+    from olearning_sim_amd.ops import load_hip_ops
+    ops = load_hip_ops(required=True)
+    # the smallest plane of the v6 family: K = 288, B*OH*OW = 32
+    C, IC, OC, B, H, W = 1, 32, 32, 2, 4, 4
+    assert ops.conv3x3_v6_ok(IC, OC, B, H, W, 1)
+    xp, w = _bf16(C, IC, B, H + 2, W + 2), _bf16(C, OC, IC, 3, 3)
+    dy, dyp = _bf16(C, OC, B, H, W), _bf16(C, OC, B, H + 2, W + 2)
+    assert ops.conv3x3_fwd_p(xp, w, 1).shape == dy.shape
+    assert ops.conv3x3_dgrad_p(dyp, w, H, W, 1).shape == (C, IC, B, H, W)
+    assert ops.conv3x3_wgrad_p(xp, dy, 1).shape == w.shape
+    m = "conv3x3"
+    _rejects(ops.conv3x3_fwd_p, xp, w.float(), 1, match=m)
+    _rejects(ops.conv3x3_dgrad_p, dyp, w.float(), H, W, 1, match=m)
+    _rejects(ops.conv3x3_wgrad_p, xp, dy.float(), 1, match=m)
+    # dy_pad with the wrong OC; dy and dy_pad with the wrong plane
+    _rejects(ops.conv3x3_dgrad_p, _bf16(C, OC * 2, B, H + 2, W + 2), w, H, W,
+             1, match=m)
+    _rejects(ops.conv3x3_wgrad_p, xp, _bf16(C, OC, B, H, W * 2), 1, match=m)
+    _rejects(ops.conv3x3_wgrad_p, xp, dyp, 1, match=m)  # a padded dy
+    _rejects(ops.conv3x3_dgrad_p, dy, w, H, W, 1, match=m)  # no halo
+    # stride 2 wants the halo round the H/2 x W/2 plane
+    _rejects(ops.conv3x3_dgrad_p, dyp, w, 2 * H, 2 * W + 2, 2, match=m)
+    # w with the wrong C
+    _rejects(ops.conv3x3_fwd_p, xp, _bf16(C + 1, OC, IC, 3, 3), 1, match=m)
+    _rejects(ops.conv3x3_dgrad_p, dyp, _bf16(C + 1, OC, IC, 3, 3), H, W, 1,
+             match=m)
+    torch.cuda.synchronize()
+
+
+def test_conv5x5_wrappers_reject_mismatched_operands():
+    from olearning_sim_amd.ops import load_hip_ops
+    from olearning_sim_amd.ops.conv import _ntab
+    ops = load_hip_ops(required=True)
+    C, IC, OC, B, H, W = 1, 2, 3, 2, 8, 8          # B*OH*OW = 32
+    OH, OW = H - 4, W - 4
+    x, w, bias = _bf16(C, IC, B, H, W), _bf16(C, OC, IC, 5, 5), _bf16(C, OC)
+    dy, dyp = _bf16(C, OC, B, OH, OW), _bf16(C, OC, B, H + 4, W + 4)
+    nt = _ntab(B, OH, OW, H, W, x.device)
+    ntd = _ntab(B, H, W, H + 4, W + 4, x.device)
+    assert ops.conv5x5_fwd(x, w, bias, nt, False).shape == dy.shape
+    assert ops.conv5x5_dgrad(dyp, w, ntd, H, W).shape == x.shape
+    assert ops.conv5x5_wgrad(x, dy, nt).shape == w.shape
+    m = "conv5x5"
+    _rejects(ops.conv5x5_fwd, x, w.float(), bias, nt, False, match=m)
+    _rejects(ops.conv5x5_dgrad, dyp, w.float(), ntd, H, W, match=m)
+    _rejects(ops.conv5x5_wgrad, x, dy.float(), nt, match=m)
+    # dy_pad with the wrong OC; dy with the wrong plane; dy_pad without
+    # the halo of 4
+    _rejects(ops.conv5x5_dgrad, _bf16(C, OC + 1, B, H + 4, W + 4), w, ntd, H,
+             W, match=m)
+    _rejects(ops.conv5x5_wgrad, x, _bf16(C, OC, B, OH, OW + 1), nt, match=m)
+    _rejects(ops.conv5x5_dgrad, dy, w, ntd, H, W, match=m)
+    # w with the wrong C; not 5x5
+    _rejects(ops.conv5x5_fwd, x, _bf16(C + 1, OC, IC, 5, 5), bias, nt, False,
+             match=m)
+    _rejects(ops.conv5x5_dgrad, dyp, _bf16(C + 1, OC, IC, 5, 5), ntd, H, W,
+             match=m)
+    _rejects(ops.conv5x5_fwd, x, _bf16(C, OC, IC, 3, 3), bias, nt, False,
+             match=m)
+    # an offset table for another plane
+    _rejects(ops.conv5x5_fwd, x, w, bias, ntd, False, match=m)
+    _rejects(ops.conv5x5_wgrad, x, dy, ntd, match=m)
+    torch.cuda.synchronize()
