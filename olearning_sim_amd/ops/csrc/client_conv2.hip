@@ -23,10 +23,18 @@
 //
 // GEMM structure per (client, m-tile, n-tile) workgroup is v5's:
 // BM=64 (4 waves x 16 rows), BN=128, BK=32, A-operand read directly
-// from global (16 B/lane/K-step), B tile double-buffered in LDS
-// [n][k+pad] so fragments are aligned ds_read_b128, one barrier per
-// K-step, register-double-buffered gather (loads for step k+1 issue
-// before the MFMAs of step k).
+// from global (16 B/lane/K-step), B tile double-buffered in LDS, one
+// barrier per K-step, register-double-buffered gather (loads for step
+// k+1 issue before the MFMAs of step k).  The B tile is k-major with
+// transposed fragment reads in the stride-1 fwd / dgrad kernels (KM,
+// below) and [n][k+pad] with aligned ds_read_b128 fragments elsewhere.
+// fwd_v6 / fwd_v7 / dgrad_v6 are compiled for exactly 4 waves per SIMD
+// (amdgpu_waves_per_eu): the residency their LDS and 256-thread blocks
+// give anyway.  Without it hipcc splits the 32 accumulators between
+// VGPRs and AGPRs, copies them across every K-step (64 v_accvgpr moves)
+// and, short of registers, waits for each fragment read before the one
+// MFMA that uses it; with it the accumulators stay in VGPRs and the
+// fragment reads are issued in batches ahead of the MFMAs.
 //
 // Replaces the role of MIOpen grouped conv on the simulator's hot path
 // (reference delegates all compute to operator subprocesses,
@@ -68,22 +76,121 @@ __device__ __forceinline__ bool xcd_remap6(int lid, int C, int T,
 }
 
 // ---------------------------------------------------------------------------
+// k-major B tile for the stride-1 kernels (template argument KM).
+//
+// The [n][k+pad] tile takes one ds_write_b16 per gathered element: a
+// thread owns one k and 16 (or 32) consecutive n, so nothing it holds is
+// contiguous in that tile.  Stored [k][n] instead, its 16 n are the 32
+// bytes the two global loads delivered, committed as two ds_write_b128,
+// and ds_read_b64_tr_b16 (gfx950) hands the MFMA the B fragment
+// transposed: lane 16g+i gets column i, rows 8g..8g+7 — the operand map
+// of the ds_read_b128 it replaces, so the same 8 k enter the same MFMA
+// in the same order and results are bit-identical.
+//
+// Image, in shorts, of a BK x 128 tile (BK*256 bytes, 16-byte aligned):
+//   off(row, nt, h) = nt*BK*16 + 16*row' + 8*(h ^ s)
+//   row' = row ^ (4 if row & 8),  s = (row' >> 2) & 1
+// nt is the 16-column n-tile, h the 16-byte half of its 32-byte row.
+// Each n-tile is a dense [BK][16] block, so nt is an immediate offset
+// on one base address per read.  Banks, by the rules of
+// MI355X_MICROARCH.md (LDS):
+//  - ds_read_b64_tr_b16 conflicts per 32-lane half over 64 banks.  A
+//    half reads rows {r..r+3} and {r+8..r+11} (r = 0 or 4, +16 for the
+//    upper half) of one n-tile, 2 x 128 bytes.  Plain 32-byte rows would
+//    put the two blocks 256 bytes apart, on the same banks; row' moves
+//    the second block by 128 bytes, so the 32 lanes cover 256 contiguous
+//    bytes mod 256: conflict-free.
+//  - ds_write_b128 conflicts per 8 consecutive lanes over 32 banks.  The
+//    8 lanes hold 8 consecutive k of one n-tile and store the same half:
+//    at a 32-byte pitch rows i and i+4 would share banks; s swaps the
+//    halves of rows 4..7, so the 8 stores cover 128 contiguous bytes
+//    mod 128: conflict-free.
+// The transposed read needs EXEC all ones and 8-byte-aligned addresses
+// (cdna_hip_programming.md T10, G17): the tiles are aligned(16), every
+// lane reads an address inside the tile, and the only exit before the
+// main loop is the block-uniform xcd_remap6 return.
+typedef __attribute__((ext_vector_type(4))) short bf16x4;
+typedef __attribute__((ext_vector_type(4), aligned(2))) ushort u16x4_u;
+typedef __attribute__((ext_vector_type(8), aligned(2))) ushort u16x8_u;
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+
+__device__ __forceinline__ int km_row(int row) {
+  return row ^ ((row >> 1) & 4);
+}
+
+// NCOL gathered columns of one k, packed as loaded: v[i] holds columns
+// 8i .. 8i+7.  The runs are 2-byte aligned (dw shifts them by one
+// element); the unaligned vector types keep them single global loads.
+template <int NCOL>
+struct KmRun {
+  uint4 v[NCOL / 8];
+  // columns 8i .. 8i+7 from row[0..7]
+  __device__ __forceinline__ void load8(int i, const ushort* row) {
+    v[i] = __builtin_bit_cast(uint4,
+                              *reinterpret_cast<const u16x8_u*>(row));
+  }
+  // columns 4i .. 4i+3 from row[0..3]
+  __device__ __forceinline__ void load4(int i, const ushort* row) {
+    const uint2 t =
+        __builtin_bit_cast(uint2, *reinterpret_cast<const u16x4_u*>(row));
+    if (i & 1) { v[i >> 1].z = t.x; v[i >> 1].w = t.y; }
+    else       { v[i >> 1].x = t.x; v[i >> 1].y = t.y; }
+  }
+};
+
+// commit row kk of n-tile nt: two ds_write_b128, data as loaded
+template <int BK>
+__device__ __forceinline__ void km_store(short* tile, int kk, int nt,
+                                         const uint4& lo, const uint4& hi) {
+  const int rp = km_row(kk);
+  const int s = (rp >> 2) & 1;
+  short* p = tile + nt * (BK * 16) + 16 * rp;
+  *reinterpret_cast<uint4*>(p + 8 * s) = lo;
+  *reinterpret_cast<uint4*>(p + 8 * (s ^ 1)) = hi;
+}
+
+// per-lane offset (shorts) of the transposed read of rows r0+8g+q
+// (lane = 16g+4q+p) inside n-tile 0; r0 = 0 or 4, +32 rows = +512
+__device__ __forceinline__ int km_frag_off(int lane, int r0) {
+  const int p = lane & 3;
+  const int rp = km_row(r0 + 8 * (lane >> 4) + ((lane >> 2) & 3));
+  const int s = (rp >> 2) & 1;
+  return 16 * rp + 8 * ((p >> 1) ^ s) + 4 * (p & 1);
+}
+
+// B fragment of n-tile nt, k rows krow0 .. krow0+31 (krow0 = 0 or 32)
+template <int BK>
+__device__ __forceinline__ bf16x8 km_frag(const short* tile, int off_lo,
+                                          int off_hi, int nt, int krow0) {
+  const short* base = tile + nt * (BK * 16) + krow0 * 16;
+  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_bf16x4*)(base + off_lo));
+  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_bf16x4*)(base + off_hi));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// ---------------------------------------------------------------------------
 // fwd v6: y[c][oc][n] = sum_k W[c][oc][k] * x_pad[c][ic][b][oh*s+dh][ow*s+dw]
 // (k = (ic,dh,dw), dw fastest).
 //
 // LG_OW: 2 or 3 hoist (b,oh) per sub-row of 4/8 columns; 4 = "OW >= 16",
 // whole 16-column segment in one output row.
-template <int LG_OW_T, int STRIDE>
-__global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v6(
+// KM: k-major B tile (above), stride 1 only; false = the [n][k+pad] tile.
+template <int LG_OW_T, int STRIDE, bool KM = false>
+__global__ __launch_bounds__(CONV_THREADS)
+__attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v6(
     const __hip_bfloat16* __restrict__ xp, const __hip_bfloat16* __restrict__ w,
     __hip_bfloat16* __restrict__ y, ConvGeom6 g) {
+  static_assert(!KM || STRIDE == 1, "k-major staging needs contiguous runs");
   int c, tile;
   if (!xcd_remap6(blockIdx.x, g.C, g.tiles_m * g.tiles_n, c, tile)) return;
   const int mt = tile / g.tiles_n;
   const int m0 = mt * CV6_BM;
   const int n0 = (tile - mt * g.tiles_n) * CV6_BN;
 
-  __shared__ short bT_lds[2][CV6_BN * (CV6_BK + CV6_PAD)];
+  __shared__ __attribute__((aligned(16))) short
+      bT_lds[2][CV6_BN * (KM ? CV6_BK : CV6_BK + CV6_PAD)];
   const int K = g.IC * 9;
   const int N = g.B * g.OH * g.OW;
   const int HpWp = g.Hp * g.Wp;
@@ -105,7 +212,9 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v6(
 
   const int kk = threadIdx.x % CV6_BK;
   const int nn0 = (threadIdx.x / CV6_BK) * (CV6_BN / 8);
-  ushort breg[CV6_BN / 8];
+  ushort breg[CV6_BN / 8];                  // !KM
+  KmRun<CV6_BN / 8> brun;                   // KM
+  const int foff_lo = km_frag_off(lane, 0), foff_hi = km_frag_off(lane, 4);
 
   auto gather = [&](int k0) {
     const int k = k0 + kk;                  // < K (K % BK == 0)
@@ -121,8 +230,13 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v6(
       int ow0 = min(q & ((1 << g.lg_ow) - 1), g.OW - CV6_BN / 8);
       const ushort* row = plane + (int64_t)b * HpWp
                           + (oh * STRIDE + dh) * g.Wp + ow0 * STRIDE + dw;
+      if constexpr (KM) {
+        brun.load8(0, row);
+        brun.load8(1, row + 8);
+      } else {
 #pragma unroll
-      for (int j = 0; j < CV6_BN / 8; ++j) breg[j] = row[j * STRIDE];
+        for (int j = 0; j < CV6_BN / 8; ++j) breg[j] = row[j * STRIDE];
+      }
     } else {
       // OW = 4 or 8: hoist per sub-row of OW columns
       constexpr int SUBW = 1 << LG_OW_T;
@@ -135,38 +249,61 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v6(
         int oh = q >> LG_OW_T;
         const ushort* row = plane + (int64_t)b * HpWp
                             + (oh * STRIDE + dh) * g.Wp + dw;
+        if constexpr (KM) {
+          if (SUBW == 8) brun.load8(rr, row);
+          else brun.load4(rr, row);
+        } else {
 #pragma unroll
-        for (int j = 0; j < SUBW; ++j)
-          breg[rr * SUBW + j] = row[j * STRIDE];
+          for (int j = 0; j < SUBW; ++j)
+            breg[rr * SUBW + j] = row[j * STRIDE];
+        }
       }
     }
   };
   auto commit = [&](int buf) {
+    if constexpr (KM) {
+      km_store<CV6_BK>(bT_lds[buf], kk, nn0 / 16, brun.v[0], brun.v[1]);
+    } else {
 #pragma unroll
-    for (int j = 0; j < CV6_BN / 8; ++j)
-      bT_lds[buf][(nn0 + j) * (CV6_BK + CV6_PAD) + kk] = (short)breg[j];
+      for (int j = 0; j < CV6_BN / 8; ++j)
+        bT_lds[buf][(nn0 + j) * (CV6_BK + CV6_PAD) + kk] = (short)breg[j];
+    }
+  };
+
+  // The A fragment of step k+1 is loaded one step ahead, AFTER that
+  // step's gather: vmcnt counts in issue order, so the commit waits for
+  // the gather alone and the MFMAs never wait for a load issued in their
+  // own step (loaded in place, A's wait also drained the gather just
+  // issued in front of it).
+  auto load_a = [&](int k0) {
+    return *reinterpret_cast<const uint4*>(wrow + k0 + 8 * (lane >> 4));
+  };
+  // rows past OC are zeroed at use, so the load is not waited for here
+  auto use_a = [&](uint4 av) {
+    if (!arow_ok) av = make_uint4(0, 0, 0, 0);
+    return __builtin_bit_cast(bf16x8, av);
   };
 
   gather(0);
+  uint4 a_next = load_a(0);
   commit(0);
   int cur = 0;
   for (int k0 = 0; k0 < K; k0 += CV6_BK) {
     __syncthreads();
-    if (k0 + CV6_BK < K) gather(k0 + CV6_BK);
-    bf16x8 a;
-    {
-      uint4 av = *reinterpret_cast<const uint4*>(wrow + k0 + 8 * (lane >> 4));
-      a = *reinterpret_cast<const bf16x8*>(&av);
-      if (!arow_ok) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] = 0;
-      }
+    const bf16x8 a = use_a(a_next);
+    if (k0 + CV6_BK < K) {
+      gather(k0 + CV6_BK);
+      a_next = load_a(k0 + CV6_BK);
     }
 #pragma unroll
     for (int nt = 0; nt < CV6_BN / 16; ++nt) {
-      bf16x8 b = *reinterpret_cast<const bf16x8*>(
-          &bT_lds[cur][(nt * 16 + (lane & 15)) * (CV6_BK + CV6_PAD)
-                       + 8 * (lane >> 4)]);
+      bf16x8 b;
+      if constexpr (KM)
+        b = km_frag<CV6_BK>(bT_lds[cur], foff_lo, foff_hi, nt, 0);
+      else
+        b = *reinterpret_cast<const bf16x8*>(
+            &bT_lds[cur][(nt * 16 + (lane & 15)) * (CV6_BK + CV6_PAD)
+                         + 8 * (lane >> 4)]);
       acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nt], 0, 0, 0);
     }
     if (k0 + CV6_BK < K) commit(cur ^ 1);
@@ -317,11 +454,14 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v8(
 // 8 MFMAs; cdna_hip_programming.md: BK 32->64 = +7..16% on the dense
 // GEMM ladder), with s_setprio(1) around the MFMA cluster (T5).
 // Requires K % 64 == 0 (IC a multiple of 64); launcher falls back to
-// v6 otherwise.
-template <int LG_OW_T, int STRIDE>
-__global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v7(
+// v6 otherwise.  KM as in fwd v6: a thread's 32 columns are two n-tiles,
+// four ds_write_b128.
+template <int LG_OW_T, int STRIDE, bool KM = false>
+__global__ __launch_bounds__(CONV_THREADS)
+__attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v7(
     const __hip_bfloat16* __restrict__ xp, const __hip_bfloat16* __restrict__ w,
     __hip_bfloat16* __restrict__ y, ConvGeom6 g) {
+  static_assert(!KM || STRIDE == 1, "k-major staging needs contiguous runs");
   constexpr int BK = 64;
   int c, tile;
   if (!xcd_remap6(blockIdx.x, g.C, g.tiles_m * g.tiles_n, c, tile)) return;
@@ -329,7 +469,8 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v7(
   const int m0 = mt * CV6_BM;
   const int n0 = (tile - mt * g.tiles_n) * CV6_BN;
 
-  __shared__ short bT_lds[2][CV6_BN * (BK + CV6_PAD)];
+  __shared__ __attribute__((aligned(16))) short
+      bT_lds[2][CV6_BN * (KM ? BK : BK + CV6_PAD)];
   const int K = g.IC * 9;
   const int N = g.B * g.OH * g.OW;
   const int HpWp = g.Hp * g.Wp;
@@ -351,7 +492,9 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v7(
 
   const int kk = threadIdx.x & 63;           // staged k-row
   const int nn0 = (threadIdx.x >> 6) * 32;   // 32 cols per thread
-  ushort breg[32];
+  ushort breg[32];                           // !KM
+  KmRun<32> brun;                            // KM
+  const int foff_lo = km_frag_off(lane, 0), foff_hi = km_frag_off(lane, 4);
 
   auto gather = [&](int k0) {
     const int k = k0 + kk;
@@ -360,6 +503,7 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v7(
     const ushort* plane = xc + (int64_t)ic * planeB;
     constexpr int SUBW = 1 << (LG_OW_T < 5 ? LG_OW_T : 5);
     constexpr int NROW = 32 / SUBW;
+    static_assert(!KM || SUBW >= 8, "k-major runs are whole 8-column loads");
 #pragma unroll
     for (int rr = 0; rr < NROW; ++rr) {
       int n = min(n0 + nn0 + rr * SUBW, N - 1);
@@ -371,41 +515,64 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v7(
       else ow0 = min(ow0, g.OW - 32);
       const ushort* row = plane + (int64_t)b * HpWp
                           + (oh * STRIDE + dh) * g.Wp + ow0 * STRIDE + dw;
+      if constexpr (KM) {
 #pragma unroll
-      for (int j = 0; j < SUBW; ++j)
-        breg[rr * SUBW + j] = row[j * STRIDE];
+        for (int j = 0; j < SUBW / 8; ++j)
+          brun.load8(rr * (SUBW / 8) + j, row + 8 * j);
+      } else {
+#pragma unroll
+        for (int j = 0; j < SUBW; ++j)
+          breg[rr * SUBW + j] = row[j * STRIDE];
+      }
     }
   };
   auto commit = [&](int buf) {
+    if constexpr (KM) {
+      km_store<BK>(bT_lds[buf], kk, nn0 / 16, brun.v[0], brun.v[1]);
+      km_store<BK>(bT_lds[buf], kk, nn0 / 16 + 1, brun.v[2], brun.v[3]);
+    } else {
 #pragma unroll
-    for (int j = 0; j < 32; ++j)
-      bT_lds[buf][(nn0 + j) * (BK + CV6_PAD) + kk] = (short)breg[j];
+      for (int j = 0; j < 32; ++j)
+        bT_lds[buf][(nn0 + j) * (BK + CV6_PAD) + kk] = (short)breg[j];
+    }
+  };
+
+  // A one step ahead and after the gather, as in fwd v6
+  auto load_a = [&](int k0, int sub) {
+    return *reinterpret_cast<const uint4*>(
+        wrow + k0 + sub * 32 + 8 * (lane >> 4));
+  };
+  // rows past OC are zeroed at use, so the load is not waited for here
+  auto use_a = [&](uint4 av) {
+    if (!arow_ok) av = make_uint4(0, 0, 0, 0);
+    return __builtin_bit_cast(bf16x8, av);
   };
 
   gather(0);
+  uint4 a_next[2] = {load_a(0, 0), load_a(0, 1)};
   commit(0);
   int cur = 0;
   for (int k0 = 0; k0 < K; k0 += BK) {
     __syncthreads();
-    if (k0 + BK < K) gather(k0 + BK);
+    const uint4 a_cur[2] = {a_next[0], a_next[1]};
+    if (k0 + BK < K) {
+      gather(k0 + BK);
+      a_next[0] = load_a(k0 + BK, 0);
+      a_next[1] = load_a(k0 + BK, 1);
+    }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
-      bf16x8 a;
-      {
-        uint4 av = *reinterpret_cast<const uint4*>(
-            wrow + k0 + sub * 32 + 8 * (lane >> 4));
-        a = *reinterpret_cast<const bf16x8*>(&av);
-        if (!arow_ok) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) a[e] = 0;
-        }
-      }
+      const bf16x8 a = use_a(a_cur[sub]);
 #pragma unroll
       for (int nt = 0; nt < CV6_BN / 16; ++nt) {
-        bf16x8 b = *reinterpret_cast<const bf16x8*>(
-            &bT_lds[cur][(nt * 16 + (lane & 15)) * (BK + CV6_PAD)
-                         + sub * 32 + 8 * (lane >> 4)]);
+        bf16x8 b;
+        if constexpr (KM)
+          b = km_frag<BK>(bT_lds[cur], foff_lo, foff_hi, nt, sub * 32);
+        else
+          b = *reinterpret_cast<const bf16x8*>(
+              &bT_lds[cur][(nt * 16 + (lane & 15)) * (BK + CV6_PAD)
+                           + sub * 32 + 8 * (lane >> 4)]);
         acc[nt] =
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nt], 0, 0, 0);
       }
@@ -433,8 +600,10 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v7(
 // flip folded into the A staging (A[ic][k] = W[oc][ic][8-(3dh+dw)]) —
 // no host-side weight transform, W is read once through L2.
 // B gather = fwd's padded gather over dy_pad (output plane = H,W of dX).
-template <int LG_OW_T>
-__global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_dgrad_v6(
+// KM: k-major B tile as in fwd v6; the A staging is the same either way.
+template <int LG_OW_T, bool KM = false>
+__global__ __launch_bounds__(CONV_THREADS)
+__attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_dgrad_v6(
     const __hip_bfloat16* __restrict__ dyp, const __hip_bfloat16* __restrict__ w,
     __hip_bfloat16* __restrict__ dx, ConvGeom6 g) {
   // geometry: OH/OW here are dX's plane (the gather output), Hp/Wp the
@@ -445,8 +614,9 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_dgrad_v6(
   const int m0 = mt * CV6_BM;
   const int n0 = (tile - mt * g.tiles_n) * CV6_BN;
 
-  __shared__ short a_lds[2][CV6_BM * CV6_BK];
-  __shared__ short bT_lds[2][CV6_BN * (CV6_BK + CV6_PAD)];
+  __shared__ __attribute__((aligned(16))) short a_lds[2][CV6_BM * CV6_BK];
+  __shared__ __attribute__((aligned(16))) short
+      bT_lds[2][CV6_BN * (KM ? CV6_BK : CV6_BK + CV6_PAD)];
   const int K = g.OC * 9;
   const int N = g.B * g.OH * g.OW;
   const int HpWp = g.Hp * g.Wp;
@@ -469,7 +639,9 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_dgrad_v6(
   const int ak0 = (threadIdx.x % 4) * 8;
   const int aic = min(m0 + amm, g.IC - 1);
   const bool aic_ok = (m0 + amm) < g.IC;
-  ushort breg[CV6_BN / 8];
+  ushort breg[CV6_BN / 8];                      // !KM
+  KmRun<CV6_BN / 8> brun;                       // KM
+  const int foff_lo = km_frag_off(lane, 0), foff_hi = km_frag_off(lane, 4);
   ushort areg[8];
 
   auto gather = [&](int k0) {
@@ -501,8 +673,13 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_dgrad_v6(
         int ow0 = min(q & ((1 << g.lg_ow) - 1), g.OW - CV6_BN / 8);
         const ushort* row = plane + (int64_t)b * HpWp + (oh + dh) * g.Wp
                             + ow0 + dw;
+        if constexpr (KM) {
+          brun.load8(0, row);
+          brun.load8(1, row + 8);
+        } else {
 #pragma unroll
-        for (int j = 0; j < CV6_BN / 8; ++j) breg[j] = row[j];
+          for (int j = 0; j < CV6_BN / 8; ++j) breg[j] = row[j];
+        }
       } else {
         constexpr int SUBW = 1 << LG_OW_T;
         constexpr int NROW = (CV6_BN / 8) / SUBW;
@@ -513,8 +690,13 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_dgrad_v6(
           int q = n & ((1 << g.lg_ohw) - 1);
           int oh = q >> LG_OW_T;
           const ushort* row = plane + (int64_t)b * HpWp + (oh + dh) * g.Wp + dw;
+          if constexpr (KM) {
+            if (SUBW == 8) brun.load8(rr, row);
+            else brun.load4(rr, row);
+          } else {
 #pragma unroll
-          for (int j = 0; j < SUBW; ++j) breg[rr * SUBW + j] = row[j];
+            for (int j = 0; j < SUBW; ++j) breg[rr * SUBW + j] = row[j];
+          }
         }
       }
     }
@@ -523,9 +705,13 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_dgrad_v6(
 #pragma unroll
     for (int j = 0; j < 8; ++j)
       a_lds[buf][amm * CV6_BK + ak0 + j] = (short)areg[j];
+    if constexpr (KM) {
+      km_store<CV6_BK>(bT_lds[buf], kk, nn0 / 16, brun.v[0], brun.v[1]);
+    } else {
 #pragma unroll
-    for (int j = 0; j < CV6_BN / 8; ++j)
-      bT_lds[buf][(nn0 + j) * (CV6_BK + CV6_PAD) + kk] = (short)breg[j];
+      for (int j = 0; j < CV6_BN / 8; ++j)
+        bT_lds[buf][(nn0 + j) * (CV6_BK + CV6_PAD) + kk] = (short)breg[j];
+    }
   };
 
   gather(0);
@@ -538,9 +724,13 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_dgrad_v6(
         &a_lds[cur][(wave * 16 + (lane & 15)) * CV6_BK + 8 * (lane >> 4)]);
 #pragma unroll
     for (int nt = 0; nt < CV6_BN / 16; ++nt) {
-      bf16x8 b = *reinterpret_cast<const bf16x8*>(
-          &bT_lds[cur][(nt * 16 + (lane & 15)) * (CV6_BK + CV6_PAD)
-                       + 8 * (lane >> 4)]);
+      bf16x8 b;
+      if constexpr (KM)
+        b = km_frag<CV6_BK>(bT_lds[cur], foff_lo, foff_hi, nt, 0);
+      else
+        b = *reinterpret_cast<const bf16x8*>(
+            &bT_lds[cur][(nt * 16 + (lane & 15)) * (CV6_BK + CV6_PAD)
+                         + 8 * (lane >> 4)]);
       acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nt], 0, 0, 0);
     }
     if (k0 + CV6_BK < K) commit(cur ^ 1);
@@ -1365,6 +1555,11 @@ extern "C" const char* ols_conv3x3_route(int dir, int IC, int OC, int B,
   return conv3_route_name(conv3_route(dir, IC, OC, B, H, W, stride));
 }
 
+extern "C" const char* ols_conv3x3_staging(int dir, int IC, int OC, int B,
+                                           int H, int W, int stride) {
+  return conv3_kmajor(dir, IC, OC, B, H, W, stride) ? "kmajor" : "nmajor";
+}
+
 extern "C" void ols_conv3x3_fwd_p(const void* xp, const void* w, void* y,
                                   int C, int IC, int OC, int B, int H, int W,
                                   int stride, hipStream_t stream) {
@@ -1373,16 +1568,21 @@ extern "C" void ols_conv3x3_fwd_p(const void* xp, const void* w, void* y,
   g.tiles_m = conv3_cdiv(OC, CV6_BM);
   g.tiles_n = conv3_cdiv(B * g.OH * g.OW, CV6_BN);
   ConvKernel6 k = nullptr;
-  switch (conv3_route_fwd_v6(IC, OC, B, H, W, stride)) {
-    case CV3_FWD_V6_2_1: k = k_conv3x3_fwd_v6<2, 1>; break;
-    case CV3_FWD_V6_3_1: k = k_conv3x3_fwd_v6<3, 1>; break;
-    case CV3_FWD_V6_4_1: k = k_conv3x3_fwd_v6<4, 1>; break;
+  const Conv3Route route = conv3_route_fwd_v6(IC, OC, B, H, W, stride);
+  const bool km = conv3_kmajor_v6(0, route);
+#define KM_CASE(id, kern, ...)                                              \
+  case id: k = km ? kern<__VA_ARGS__, true> : kern<__VA_ARGS__, false>; break;
+  switch (route) {
+    KM_CASE(CV3_FWD_V6_2_1, k_conv3x3_fwd_v6, 2, 1)
+    KM_CASE(CV3_FWD_V6_3_1, k_conv3x3_fwd_v6, 3, 1)
+    KM_CASE(CV3_FWD_V6_4_1, k_conv3x3_fwd_v6, 4, 1)
     case CV3_FWD_V6_2_2: k = k_conv3x3_fwd_v6<2, 2>; break;
     case CV3_FWD_V6_3_2: k = k_conv3x3_fwd_v6<3, 2>; break;
     case CV3_FWD_V6_4_2: k = k_conv3x3_fwd_v6<4, 2>; break;
+    // [n][k] only: measured no faster k-major (conv3_kmajor_v6)
     case CV3_FWD_V7_3_1: k = k_conv3x3_fwd_v7<3, 1>; break;
-    case CV3_FWD_V7_4_1: k = k_conv3x3_fwd_v7<4, 1>; break;
-    case CV3_FWD_V7_5_1: k = k_conv3x3_fwd_v7<5, 1>; break;
+    KM_CASE(CV3_FWD_V7_4_1, k_conv3x3_fwd_v7, 4, 1)
+    KM_CASE(CV3_FWD_V7_5_1, k_conv3x3_fwd_v7, 5, 1)
     case CV3_FWD_V8_2_1: k = k_conv3x3_fwd_v8<2, 1>; break;
     case CV3_FWD_V8_3_1: k = k_conv3x3_fwd_v8<3, 1>; break;
     case CV3_FWD_V8_4_1: k = k_conv3x3_fwd_v8<4, 1>; break;
@@ -1416,10 +1616,12 @@ extern "C" void ols_conv3x3_dgrad_p(const void* dyp, const void* w, void* dx,
   g.tiles_m = conv3_cdiv(IC, CV6_BM);
   g.tiles_n = conv3_cdiv(B * g.OH * g.OW, CV6_BN);
   ConvKernel6 k = nullptr;
-  switch (conv3_route_dgrad_v6(IC, OC, B, H, W, stride)) {
-    case CV3_DGRAD_V6_2: k = k_conv3x3_dgrad_v6<2>; break;
-    case CV3_DGRAD_V6_3: k = k_conv3x3_dgrad_v6<3>; break;
-    case CV3_DGRAD_V6_4: k = k_conv3x3_dgrad_v6<4>; break;
+  const Conv3Route route = conv3_route_dgrad_v6(IC, OC, B, H, W, stride);
+  const bool km = conv3_kmajor_v6(1, route);
+  switch (route) {
+    KM_CASE(CV3_DGRAD_V6_2, k_conv3x3_dgrad_v6, 2)
+    KM_CASE(CV3_DGRAD_V6_3, k_conv3x3_dgrad_v6, 3)
+    KM_CASE(CV3_DGRAD_V6_4, k_conv3x3_dgrad_v6, 4)
     case CV3_DGRAD_V7_2: k = k_conv3x3_dgrad_v7<2>; break;
     case CV3_DGRAD_V7_3: k = k_conv3x3_dgrad_v7<3>; break;
     case CV3_DGRAD_V7_4: k = k_conv3x3_dgrad_v7<4>; break;
@@ -1429,6 +1631,7 @@ extern "C" void ols_conv3x3_dgrad_p(const void* dyp, const void* w, void* dx,
     case CV3_DGRAD_S2_4: launch_s2<4>(dyp, w, dx, g, stream); return;
     default: return;                    // not a v6-family dgrad route
   }
+#undef KM_CASE
   launch6(k, dyp, w, dx, g, stream);
 }
 

@@ -49,13 +49,14 @@ static inline const char* conv3_route_name(Conv3Route r) {
   return names[r];
 }
 
-// The four A/B switches, read on every call.  OLSIM_CONV_V=5 sends every
-// shape to the v5 family; the other three act on presence, whatever the
+// The five A/B switches, read on every call.  OLSIM_CONV_V=5 sends every
+// shape to the v5 family; the other four act on presence, whatever the
 // value (OLSIM_CONV_DW8=0 restores the scalar wgrad gather because it is
 // set): OLSIM_CONV_V8 the two-ahead fwd_v8, OLSIM_CONV_DW64 the BK=64
-// dgrad_v7 / wgrad_v7, OLSIM_CONV_DW8 no run-vectorised wgrad_v8 / v8s.
+// dgrad_v7 / wgrad_v7, OLSIM_CONV_DW8 no run-vectorised wgrad_v8 / v8s,
+// OLSIM_CONV_NMAJOR the [n][k] B tile in every fwd / dgrad kernel.
 struct Conv3Env {
-  bool v5, v8, dw64, no_dw8;
+  bool v5, v8, dw64, no_dw8, nmajor;
 };
 
 static inline Conv3Env conv3_env() {
@@ -63,7 +64,8 @@ static inline Conv3Env conv3_env() {
   return {v != nullptr && strcmp(v, "5") == 0,
           getenv("OLSIM_CONV_V8") != nullptr,
           getenv("OLSIM_CONV_DW64") != nullptr,
-          getenv("OLSIM_CONV_DW8") != nullptr};
+          getenv("OLSIM_CONV_DW8") != nullptr,
+          getenv("OLSIM_CONV_NMAJOR") != nullptr};
 }
 
 static inline int conv3_cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -178,6 +180,26 @@ static inline Conv3Route conv3_route_wgrad_v6(int IC, int OC, int B, int H,
   return CV3_WGRAD_V6;
 }
 
+// B-tile staging of a v6-family fwd (dir 0) or dgrad (dir 1) route: true
+// = k-major tile, 16-byte LDS stores and transposed fragment reads; false
+// = the [n][k+pad] tile and 2-byte stores.  The kernel name and its
+// <LG_OW, STRIDE> stay the route's; the staging is one more template
+// argument.  Only the stride-1 fwd_v6 / fwd_v7 / dgrad_v6 kernels have the
+// k-major form: at stride 2 a thread's columns are alternate elements,
+// and fwd_v8 / dgrad_v7 are records kept as they were measured.
+// fwd_v7<3,1> (OW = 8, the 256-channel stage) stays [n][k]: k-major
+// measured 1.3 % slower there (0.850 vs 0.839 ms at C=250,
+// profiles/conv_kmajor_r06.md), so it has no k-major instantiation.
+static inline bool conv3_kmajor_v6(int dir, Conv3Route r) {
+  if (conv3_env().nmajor) return false;
+  if (dir == 0)
+    return r == CV3_FWD_V6_2_1 || r == CV3_FWD_V6_3_1 || r == CV3_FWD_V6_4_1
+           || r == CV3_FWD_V7_4_1 || r == CV3_FWD_V7_5_1;
+  if (dir == 1)
+    return r == CV3_DGRAD_V6_2 || r == CV3_DGRAD_V6_3 || r == CV3_DGRAD_V6_4;
+  return false;
+}
+
 // dir: 0 fwd, 1 dgrad, 2 wgrad.  Includes the family decision the Python
 // dispatcher makes (ops/conv.py _v6_ok): v6 unless OLSIM_CONV_V=5 or the
 // shape is outside conv3_v6_ok.
@@ -192,4 +214,11 @@ static inline Conv3Route conv3_route(int dir, int IC, int OC, int B, int H,
               : conv3_route_dgrad_v5(IC, OC, B, H, W, stride);
   return v6 ? conv3_route_wgrad_v6(IC, OC, B, H, W, stride)
             : conv3_route_wgrad_v5(IC, OC, B, H, W, stride);
+}
+
+// staging of the kernel conv3_route() names for the shape (v5-family and
+// wgrad routes have no k-major form)
+static inline bool conv3_kmajor(int dir, int IC, int OC, int B, int H, int W,
+                                int stride) {
+  return conv3_kmajor_v6(dir, conv3_route(dir, IC, OC, B, H, W, stride));
 }

@@ -51,6 +51,9 @@ extern "C" int ols_conv3x3_v6_ok(int IC, int OC, int B, int H, int W,
 // arguments (conv3_route.h), family decision included
 extern "C" const char* ols_conv3x3_route(int dir, int IC, int OC, int B,
                                          int H, int W, int stride);
+// "kmajor" or "nmajor": the B-tile staging of the kernel that route runs
+extern "C" const char* ols_conv3x3_staging(int dir, int IC, int OC, int B,
+                                           int H, int W, int stride);
 extern "C" void ols_conv3x3_fwd_p(const void* xp, const void* w, void* y,
                                   int C, int IC, int OC, int B, int H, int W,
                                   int stride, hipStream_t stream);
