@@ -53,6 +53,33 @@ class LocalTrainer:
         assert self._cast_flat is not None, "begin_round() not called"
         return self.master.views_of(self._cast_flat)
 
+    def _attach_master_wt(self, cast: Params, params: Params, C: int) -> None:
+        """Give every 3x3 weight whose stride-1 dgrad runs as a forward
+        convolution (ops/conv.py _dgrad_p) its flipped-transposed copy for
+        the first local step.  All replicas equal the master there, so the
+        copy is the repacked master replicated: a write with no read.  The
+        SGD update keeps it current through the later steps
+        (fused_sgd_update keep_wt) and drops it at the last."""
+        import os
+        wanted = getattr(self.model, "dgrad_wt_params", None)
+        # OLSIM_DGRAD_WT=repack: the backward repacks w on every call and
+        # no copy is held ("0" is dgrad_wt_ok's to refuse)
+        if (wanted is None or self.dtype != torch.bfloat16
+                or not self._cast_flat.is_cuda
+                or os.environ.get("OLSIM_DGRAD_WT", "1") == "repack"):
+            return
+        from ..ops.conv import attach_wt, dgrad_wt_ok
+        ops = fused.load_hip_ops(required=True)
+        for k, (H, W) in wanted(cast).items():
+            OC, IC = cast[k].shape[0], cast[k].shape[1]
+            # no copy where the backward would not read it
+            if not dgrad_wt_ok(ops, OC, IC, self.batch_size, H, W):
+                continue
+            # clone: cast[k] is a view into the flat cast at any 2-byte
+            # offset, the kernel loads 16 bytes at a time
+            wt0 = ops.conv3x3_wflip(cast[k].detach().clone()[None])[0]
+            attach_wt(params[k], ops.replicate(wt0, C))
+
     def train_chunk(self, client_ids: torch.Tensor, weights: torch.Tensor,
                     round_idx: int, delta_flat: torch.Tensor,
                     wsum: Optional[float] = None) -> Dict[str, float]:
@@ -67,6 +94,7 @@ class LocalTrainer:
         params = replicate_params(cast, C)
         plist = list(params.values())
         glist = [cast[k] for k in params]
+        self._attach_master_wt(cast, params, C)
         last_loss = 0.0
         for step in range(self.local_steps):
             x, y = self.data.batch(client_ids, round_idx, step,
@@ -82,7 +110,8 @@ class LocalTrainer:
                     [p for p, _ in live], [g for _, g in live],
                     lr=self.lr, mu=self.prox_mu,
                     global_params=[cast[k] for k, g in
-                                   zip(params, grads) if g is not None])
+                                   zip(params, grads) if g is not None],
+                    keep_wt=step < self.local_steps - 1)
             if self.report_loss and step == self.local_steps - 1:
                 last_loss = float(loss.detach())
             del grads

@@ -10,6 +10,7 @@ convs run as one grouped conv per layer in the channel-grouped layout
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -112,6 +113,24 @@ class ResNet18(ClientBatchedModel):
                                params[f"{pre}.gn2.b"], res=sc,
                                res_pad=sc_pad, pad_out=pad_out)
 
+    def dgrad_wt_params(self, params: Params):
+        """{name: (H, W)} of the 3x3 weights forward_cbf convolves at
+        stride 1 and whose input needs a gradient (all but the stem and
+        each stage's strided c1), with the plane they run at: the
+        candidates for a trainer-held flipped copy (ops/conv.py _dgrad_p).
+        Whether the shape is eligible is the caller's question to
+        conv3x3_v6_ok."""
+        if os.environ.get("OLSIM_CONV", "custom") != "custom":
+            return {}
+        planes = {}
+        for s in range(4):
+            for blk in range(2):
+                for cv in ("c1", "c2"):
+                    if s > 0 and blk == 0 and cv == "c1":
+                        continue                    # stride 2: dgrad_s2
+                    planes[f"s{s}.b{blk}.{cv}.w"] = (32 >> s, 32 >> s)
+        return planes
+
     def forward_cbf(self, params: Params, x: torch.Tensor) -> torch.Tensor:
         from ..ops.conv import client_conv3x3
         from ..ops.fused import groupnorm_relu_pad
@@ -140,7 +159,6 @@ class ResNet18(ClientBatchedModel):
         # (tools/convbench3.py, profiles/): all-shape conv total
         # 30.9 ms vs 57.1 ms (0.54x).  OLSIM_CONV=miopen forces the
         # grouped-conv reference path.
-        import os
         if x.is_cuda and x.dtype == torch.bfloat16 and \
                 os.environ.get("OLSIM_CONV", "custom") == "custom":
             from ..ops.fused import hip_ops_available

@@ -62,6 +62,62 @@ def _pad(x: torch.Tensor, pad: int) -> torch.Tensor:
     return F.pad(x, (pad, pad, pad, pad))
 
 
+def attach_wt(w: torch.Tensor, wt: torch.Tensor) -> None:
+    """Hand wt = conv3x3_wflip(w) to the backward of every conv that is
+    called with this very tensor object w.  Invariant: a wt is used only
+    if it was produced from the current contents of w.  The caller vouches
+    for that now; every later writer of w must drop_wt(w) or attach the
+    new wt.  (An in-place torch op is caught by w._version as well; the
+    extension's own in-place ops are not relied on to bump it.)"""
+    w._olsim_wt = [wt, w._version]
+
+
+def drop_wt(w: torch.Tensor) -> None:
+    """w is about to change, or has: its wt is stale.  Also reaches a
+    backward that picked the holder up in its forward."""
+    held = getattr(w, "_olsim_wt", None)
+    if held is not None:
+        held[0] = None
+        w._olsim_wt = None
+
+
+def _live_wt(held, w: torch.Tensor):
+    """wt of a holder picked up from w, or None when dropped or stale."""
+    if held is None or held[0] is None or held[1] != w._version:
+        return None
+    return held[0]
+
+
+def dgrad_wt_ok(ops, OC: int, IC: int, B: int, H: int, W: int,
+                stride: int = 1) -> bool:
+    """True when the dgrad of conv3x3(x [*, IC, B, H, W], w [*, OC, IC, 3,
+    3], stride) runs as a forward convolution with the flipped-transposed
+    weights: stride 1, the swapped shape on the v6 forward route, and
+    neither OLSIM_DGRAD_WT=0 (the A/B switch) nor OLSIM_CONV_DW64 (which
+    asks for dgrad_v7 by name) set.  Read per call."""
+    import os
+    return (stride == 1 and os.environ.get("OLSIM_DGRAD_WT", "1") != "0"
+            and "OLSIM_CONV_DW64" not in os.environ
+            and bool(ops.conv3x3_v6_ok(OC, IC, B, H, W, 1)))
+
+
+def _dgrad_p(ops, dy_pad: torch.Tensor, w: torch.Tensor, H: int, W: int,
+             stride: int, held=None) -> torch.Tensor:
+    """dx of the v6 padded path.  At stride 1 the dgrad is the forward
+    convolution of dy_pad with wt = conv3x3_wflip(w) (conv3_wflip.hip),
+    bit-identical to dgrad_v6 and without its 2-byte weight gather; wt is
+    the copy attached to w (attach_wt) while it is current, or is repacked
+    here and freed on return.
+    Everything dgrad_wt_ok refuses takes conv3x3_dgrad_p."""
+    if dgrad_wt_ok(ops, w.shape[1], w.shape[2], dy_pad.shape[2], H, W,
+                   stride):
+        wt = _live_wt(held, w)
+        if wt is None:
+            wt = ops.conv3x3_wflip(w)
+        return ops.conv3x3_fwd_p(dy_pad, wt, 1)
+    return ops.conv3x3_dgrad_p(dy_pad, w, H, W, stride)
+
+
 class _Conv3x3PadFn(torch.autograd.Function):
     """v6 padded path: the kernels gather from a 1-element zero halo so
     the implicit-im2col reads carry no bounds masks (client_conv2.hip).
@@ -74,6 +130,8 @@ class _Conv3x3PadFn(torch.autograd.Function):
         y = ops.conv3x3_fwd_p(x_pad, w, stride)
         ctx.save_for_backward(x_pad, w)
         ctx.stride = stride
+        # saved_tensors hands back new objects: read the attribute here
+        ctx.wt = getattr(w, "_olsim_wt", None)
         return y
 
     @staticmethod
@@ -85,7 +143,7 @@ class _Conv3x3PadFn(torch.autograd.Function):
         H, W = x_pad.shape[3] - 2, x_pad.shape[4] - 2
         if ctx.needs_input_grad[0]:
             dy_pad = _pad(dy, 1)
-            dx = ops.conv3x3_dgrad_p(dy_pad, w, H, W, ctx.stride)
+            dx = _dgrad_p(ops, dy_pad, w, H, W, ctx.stride, ctx.wt)
         if ctx.needs_input_grad[1]:
             dw = ops.conv3x3_wgrad_p(x_pad, dy, ctx.stride)
         return dx, dw, None
@@ -112,6 +170,8 @@ class _Conv3x3GnPadFn(torch.autograd.Function):
             pad_out)
         ctx.save_for_backward(x_pad, w, h, mask, mean, rstd, gamma)
         ctx.meta = (clients, groups, res is not None, stride)
+        # saved_tensors hands back new objects: read the attribute here
+        ctx.wt = getattr(w, "_olsim_wt", None)
         # y_pad never has a gradient; do not let autograd zero-fill one
         ctx.set_materialize_grads(False)
         if not pad_out:
@@ -133,7 +193,7 @@ class _Conv3x3GnPadFn(torch.autograd.Function):
         H, W = x_pad.shape[3] - 2, x_pad.shape[4] - 2
         dx = dw = None
         if need_dx:
-            dx = ops.conv3x3_dgrad_p(dh_pad, w, H, W, stride)
+            dx = _dgrad_p(ops, dh_pad, w, H, W, stride, ctx.wt)
         if ctx.needs_input_grad[2]:
             dw = ops.conv3x3_wgrad_p(x_pad, dh, stride)
         return (dx, None, dw, dres if has_res else None, None,

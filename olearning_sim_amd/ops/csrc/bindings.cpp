@@ -321,6 +321,71 @@ at::Tensor conv3x3_wgrad_p(at::Tensor xp, at::Tensor dy, int64_t stride) {
   return dw;
 }
 
+// ---- flipped-transposed 3x3 weights (conv3_wflip.hip) ----------------------
+// wt [C, IC, OC, 3, 3] with wt[c][ic][oc][r] = w[c][oc][ic][8 - r]:
+// conv3x3_fwd_p(dy_pad, wt, 1) is the stride-1 dgrad of w.
+
+struct WflipDims {
+  int C, OC, IC;
+};
+
+// w, and every further operand, a contiguous bf16 [C, OC, IC, 3, 3] on one
+// GPU with OC and IC multiples of the kernels' 32 x 32 tile (what
+// conv3_v6_ok admits at stride 1); wt the same with OC and IC swapped
+WflipDims wflip_dims(const at::Tensor& w, const at::Tensor& g,
+                     const at::Tensor& wt) {
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() && w.dim() == 5 &&
+                  w.scalar_type() == at::kBFloat16 && w.size(3) == 3 &&
+                  w.size(4) == 3,
+              "conv3x3_wflip: w must be a contiguous bf16 [C, OC, IC, 3, 3] "
+              "GPU tensor, got ", w.scalar_type(), " ", w.sizes());
+  const int64_t C = w.size(0), OC = w.size(1), IC = w.size(2);
+  TORCH_CHECK(C > 0 && OC > 0 && IC > 0 && OC % 32 == 0 && IC % 32 == 0,
+              "conv3x3_wflip: OC and IC must be multiples of 32, got ",
+              w.sizes());
+  TORCH_CHECK(C * (OC / 32) * (IC / 32) <= INT32_MAX,
+              "conv3x3_wflip: too many tiles");
+  for (const at::Tensor* t : {&w, &g, &wt}) {
+    if (!t->defined()) continue;
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == at::kBFloat16 &&
+                    t->device() == w.device() &&
+                    reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "conv3x3_wflip: operands must be contiguous, 16-byte "
+                "aligned bf16 tensors on one GPU");
+  }
+  TORCH_CHECK(!g.defined() || g.sizes() == w.sizes(),
+              "sgd_conv3_wt: g is ", g.sizes(), ", expected ", w.sizes());
+  TORCH_CHECK(!wt.defined() ||
+                  wt.sizes() == at::IntArrayRef({C, IC, OC, 3, 3}),
+              "sgd_conv3_wt: wt is ", wt.sizes(), ", expected [", C, ", ",
+              IC, ", ", OC, ", 3, 3]");
+  return {(int)C, (int)OC, (int)IC};
+}
+
+at::Tensor conv3x3_wflip(at::Tensor w) {
+  const WflipDims d = wflip_dims(w, {}, {});
+  auto wt = at::empty({d.C, d.IC, d.OC, 3, 3}, w.options());
+  ols_conv3_wflip(w.data_ptr(), wt.data_ptr(), d.C, d.OC, d.IC,
+                  at::cuda::getCurrentCUDAStream().stream());
+  return wt;
+}
+
+void sgd_conv3_wt(at::Tensor w, at::Tensor g, at::Tensor wt, double lr) {
+  const WflipDims d = wflip_dims(w, g, wt);
+  // the three tensors have the same byte size; wt must overlap neither
+  const char* wtp = static_cast<const char*>(wt.data_ptr());
+  const int64_t nbytes = (int64_t)wt.numel() * 2;
+  for (const at::Tensor* t : {&w, &g}) {
+    const char* p = static_cast<const char*>(t->data_ptr());
+    TORCH_CHECK(p + nbytes <= wtp || wtp + nbytes <= p,
+                "sgd_conv3_wt: wt must not overlap w or g");
+  }
+  ols_sgd_conv3_wt(w.data_ptr(), g.data_ptr(), wt.data_ptr(), d.C, d.OC,
+                   d.IC, (float)lr,
+                   at::cuda::getCurrentCUDAStream().stream());
+}
+
 // ---- 5x5 VALID family (client_conv5.hip, LeNet) -------------------------
 // ntab: int32 [B*OH*OW] plane offsets (b*H*W + oh*W + ow) built host-side
 
@@ -709,6 +774,8 @@ TORCH_LIBRARY(olsim_hip, m) {
   m.def("conv3x3_fwd_p(Tensor xp, Tensor w, int stride) -> Tensor");
   m.def("conv3x3_dgrad_p(Tensor dyp, Tensor w, int H, int W, int stride) -> Tensor");
   m.def("conv3x3_wgrad_p(Tensor xp, Tensor dy, int stride) -> Tensor");
+  m.def("conv3x3_wflip(Tensor w) -> Tensor");
+  m.def("sgd_conv3_wt(Tensor(a!) w, Tensor g, Tensor(b!) wt, float lr) -> ()");
   m.def("conv5x5_route(str dir, int IC, int OC, int H, int W) -> str",
         &conv5x5_route);
   m.def("conv5x5_fwd(Tensor x, Tensor w, Tensor bias, Tensor ntab, bool relu) -> Tensor");
@@ -748,6 +815,8 @@ TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("conv3x3_fwd_p", &conv3x3_fwd_p);
   m.impl("conv3x3_dgrad_p", &conv3x3_dgrad_p);
   m.impl("conv3x3_wgrad_p", &conv3x3_wgrad_p);
+  m.impl("conv3x3_wflip", &conv3x3_wflip);
+  m.impl("sgd_conv3_wt", &sgd_conv3_wt);
   m.impl("conv5x5_fwd", &conv5x5_fwd);
   m.impl("conv5x5_dgrad", &conv5x5_dgrad);
   m.impl("conv5x5_wgrad", &conv5x5_wgrad);

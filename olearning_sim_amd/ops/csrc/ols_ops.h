@@ -64,6 +64,15 @@ extern "C" void ols_conv3x3_wgrad_p(const void* xp, const void* dy, void* dw,
                                     int C, int IC, int OC, int B, int H,
                                     int W, int stride, hipStream_t stream);
 
+// w [C, OC, IC, 3, 3] -> wt [C, IC, OC, 3, 3], taps reversed: the forward
+// weight of the stride-1 dgrad (conv3_wflip.hip).  OC, IC multiples of 32.
+extern "C" void ols_conv3_wflip(const void* w, void* wt, int C, int OC,
+                                int IC, hipStream_t stream);
+// w -= lr * g in place and wt <- wflip(updated w), one pass
+extern "C" void ols_sgd_conv3_wt(void* w, const void* g, void* wt, int C,
+                                 int OC, int IC, float lr,
+                                 hipStream_t stream);
+
 extern "C" void ols_conv5x5_fwd(const void* x, const void* w, const void* b,
                                 void* y, const int* ntab, int C, int IC,
                                 int OC, int B, int H, int W, int relu,

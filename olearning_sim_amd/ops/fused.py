@@ -79,21 +79,45 @@ def _gpu_ops(t: torch.Tensor):
     return None
 
 
+def _wt_update_ok(w: torch.Tensor, g: torch.Tensor) -> bool:
+    """What sgd_conv3_wt asks of w and g beyond their shape (a wt was
+    attached, so the shape passed conv3x3_wflip): anything else takes the
+    plain update and loses the copy."""
+    return all(t.dtype == torch.bfloat16 and t.is_contiguous()
+               and t.data_ptr() % 16 == 0 for t in (w, g))
+
+
 # ---------------------------------------------------------------------------
 def fused_sgd_update(params: Sequence[torch.Tensor],
                      grads: Sequence[torch.Tensor],
                      lr: float,
                      mu: float = 0.0,
-                     global_params: Optional[Sequence[torch.Tensor]] = None) -> None:
+                     global_params: Optional[Sequence[torch.Tensor]] = None,
+                     keep_wt: bool = False) -> None:
     """In-place SGD / FedProx step over per-client parameter tensors.
 
     params[i]: [C, ...] client replicas; grads[i] same shape;
     global_params[i]: [...] (no client dim) — required when mu > 0.
+
+    A 3x3 conv weight may carry a flipped-transposed copy for its dgrad
+    (ops/conv.py attach_wt).  With keep_wt and mu == 0 such a weight takes
+    the update kernel that rewrites the copy from the values it has just
+    computed (conv3_wflip.hip k_sgd_conv3_wt), so the copy stays current;
+    otherwise the copy is dropped before w changes.
     """
     if not params:
         return
     if params[0].is_cuda:
+        from .conv import _live_wt, attach_wt, drop_wt
         for i, (w, g) in enumerate(zip(params, grads)):
+            held = getattr(w, "_olsim_wt", None)
+            if held is not None:
+                wt = _live_wt(held, w) if keep_wt and mu == 0.0 else None
+                drop_wt(w)
+                if wt is not None and _wt_update_ok(w, g):
+                    load_hip_ops(required=True).sgd_conv3_wt(w, g, wt, lr)
+                    attach_wt(w, wt)
+                    continue
             n = w[0].numel() if w.dim() > 1 else w.numel()
             gl = (global_params[i].reshape(-1) if (global_params is not None
                                                   and mu != 0.0)
