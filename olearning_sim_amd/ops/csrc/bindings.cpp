@@ -285,6 +285,18 @@ std::string conv3x3_staging(std::string dir, int64_t IC, int64_t OC,
                              (int)stride);
 }
 
+// "64x128" or "128x64": the block tile of the kernel conv3x3_route names
+// (conv3_route.h conv3_tile; OLSIM_CONV_BM64 forces "64x128").  The
+// flipped-weight dgrad runs the forward of (OC, IC): ask for that.
+std::string conv3x3_tile(std::string dir, int64_t IC, int64_t OC, int64_t B,
+                         int64_t H, int64_t W, int64_t stride) {
+  int d = dir == "fwd" ? 0 : dir == "dgrad" ? 1 : dir == "wgrad" ? 2 : -1;
+  TORCH_CHECK(d >= 0, "conv3x3_tile: dir must be fwd, dgrad or wgrad");
+  TORCH_CHECK(stride == 1 || stride == 2, "conv3x3_tile: stride 1 or 2");
+  return ols_conv3x3_tile(d, (int)IC, (int)OC, (int)B, (int)H, (int)W,
+                          (int)stride);
+}
+
 void check_v6(const ConvDims& d, int64_t stride) {
   TORCH_CHECK(ols_conv3x3_v6_ok(d.IC, d.OC, d.B, d.H, d.W, (int)stride),
               "shape unsupported by the v6 conv path");
@@ -771,6 +783,8 @@ TORCH_LIBRARY(olsim_hip, m) {
         "int stride) -> str", &conv3x3_route);
   m.def("conv3x3_staging(str dir, int IC, int OC, int B, int H, int W, "
         "int stride) -> str", &conv3x3_staging);
+  m.def("conv3x3_tile(str dir, int IC, int OC, int B, int H, int W, "
+        "int stride) -> str", &conv3x3_tile);
   m.def("conv3x3_fwd_p(Tensor xp, Tensor w, int stride) -> Tensor");
   m.def("conv3x3_dgrad_p(Tensor dyp, Tensor w, int H, int W, int stride) -> Tensor");
   m.def("conv3x3_wgrad_p(Tensor xp, Tensor dy, int stride) -> Tensor");

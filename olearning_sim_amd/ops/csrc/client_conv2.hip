@@ -25,7 +25,11 @@
 // BM=64 (4 waves x 16 rows), BN=128, BK=32, A-operand read directly
 // from global (16 B/lane/K-step), B tile double-buffered in LDS, one
 // barrier per K-step, register-double-buffered gather (loads for step
-// k+1 issue before the MFMAs of step k).  The B tile is k-major with
+// k+1 issue before the MFMAs of step k).  The forward kernels also have a
+// BM=128 x BN=64 block (TILE, four waves of 32 rows x 64 columns) for
+// OC where it adds no padded rows: every B fragment read feeds two MFMAs
+// and the block gathers and commits half the columns per MFMA
+// (conv3_route.h conv3_tile_v6).  The B tile is k-major with
 // transposed fragment reads in the stride-1 fwd / dgrad kernels (KM,
 // below) and [n][k+pad] with aligned ds_read_b128 fragments elsewhere.
 // fwd_v6 / fwd_v7 / dgrad_v6 are compiled for exactly 4 waves per SIMD
@@ -105,6 +109,16 @@ __device__ __forceinline__ bool xcd_remap6(int lid, int C, int T,
 //    at a 32-byte pitch rows i and i+4 would share banks; s swaps the
 //    halves of rows 4..7, so the 8 stores cover 128 contiguous bytes
 //    mod 128: conflict-free.
+// The 128x64 block tile (template argument TILE of fwd v6 / v7) is the
+// same image with four n-tiles instead of eight, and both arguments were
+// re-derived for its thread maps.  Read: a wave still reads whole n-tiles
+// with km_frag_off, whichever rows it owns, so the per-half address set is
+// the one above.  Write: fwd v6 has kk = tid % 32 and 8 columns per
+// thread, (nt, h) = (grp >> 1, grp & 1) with grp = tid / 32; fwd v7 has
+// kk = tid & 63 and one n-tile per thread, both halves.  Either way 8
+// consecutive lanes share grp, so they hold 8 consecutive k (8j .. 8j+7,
+// which row' permutes among themselves) of one n-tile and store the same
+// half: the 128 contiguous bytes mod 128 of the second argument.
 // The transposed read needs EXEC all ones and 8-byte-aligned addresses
 // (cdna_hip_programming.md T10, G17): the tiles are aligned(16), every
 // lane reads an address inside the tile, and the only exit before the
@@ -137,6 +151,16 @@ struct KmRun {
     else       { v[i >> 1].x = t.x; v[i >> 1].y = t.y; }
   }
 };
+
+// commit half h (columns 8h .. 8h+7) of row kk of n-tile nt: one
+// ds_write_b128, data as loaded
+template <int BK>
+__device__ __forceinline__ void km_store_half(short* tile, int kk, int nt,
+                                              int h, const uint4& v) {
+  const int rp = km_row(kk);
+  const int s = (rp >> 2) & 1;
+  *reinterpret_cast<uint4*>(tile + nt * (BK * 16) + 16 * rp + 8 * (h ^ s)) = v;
+}
 
 // commit row kk of n-tile nt: two ds_write_b128, data as loaded
 template <int BK>
@@ -177,20 +201,29 @@ __device__ __forceinline__ bf16x8 km_frag(const short* tile, int off_lo,
 // LG_OW: 2 or 3 hoist (b,oh) per sub-row of 4/8 columns; 4 = "OW >= 16",
 // whole 16-column segment in one output row.
 // KM: k-major B tile (above), stride 1 only; false = the [n][k+pad] tile.
-template <int LG_OW_T, int STRIDE, bool KM = false>
+// TILE: 0 = 64x128 block, 16 rows per wave; 1 = 128x64, 32 rows per wave
+// (two A fragments, acc[2][4]) and 8 gathered columns per thread, half an
+// n-tile: one ds_write_b128.  Same k, same MFMA, same K order per output
+// element either way.
+template <int LG_OW_T, int STRIDE, bool KM = false, int TILE = 0>
 __global__ __launch_bounds__(CONV_THREADS)
 __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v6(
     const __hip_bfloat16* __restrict__ xp, const __hip_bfloat16* __restrict__ w,
     __hip_bfloat16* __restrict__ y, ConvGeom6 g) {
   static_assert(!KM || STRIDE == 1, "k-major staging needs contiguous runs");
+  static_assert(TILE == 0 || TILE == 1, "64x128 or 128x64");
+  constexpr int BM = TILE ? 128 : CV6_BM, BN = TILE ? 64 : CV6_BN;
+  constexpr int MI = BM / 64;               // 16-row A fragments per wave
+  constexpr int NTW = BN / 16;              // 16-column n-tiles per wave
+  constexpr int NCOL = BN / 8;              // gathered columns per thread
   int c, tile;
   if (!xcd_remap6(blockIdx.x, g.C, g.tiles_m * g.tiles_n, c, tile)) return;
   const int mt = tile / g.tiles_n;
-  const int m0 = mt * CV6_BM;
-  const int n0 = (tile - mt * g.tiles_n) * CV6_BN;
+  const int m0 = mt * BM;
+  const int n0 = (tile - mt * g.tiles_n) * BN;
 
   __shared__ __attribute__((aligned(16))) short
-      bT_lds[2][CV6_BN * (KM ? CV6_BK : CV6_BK + CV6_PAD)];
+      bT_lds[2][BN * (KM ? CV6_BK : CV6_BK + CV6_PAD)];
   const int K = g.IC * 9;
   const int N = g.B * g.OH * g.OW;
   const int HpWp = g.Hp * g.Wp;
@@ -202,18 +235,27 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v6(
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int arow = m0 + wave * 16 + (lane & 15);
-  const __hip_bfloat16* wrow = wc + (int64_t)min(arow, g.OC - 1) * K;
-  const bool arow_ok = arow < g.OC;
-
-  f32x4 acc[CV6_BN / 16];
+  // wave w owns rows m0 + 16*MI*w .. and all BN columns
+  const int wrow0 = 16 * MI * wave;
+  const __hip_bfloat16* wrow[MI];
+  bool arow_ok[MI];
 #pragma unroll
-  for (int i = 0; i < CV6_BN / 16; ++i) acc[i] = {0.f, 0.f, 0.f, 0.f};
+  for (int mi = 0; mi < MI; ++mi) {
+    const int arow = m0 + wrow0 + mi * 16 + (lane & 15);
+    wrow[mi] = wc + (int64_t)min(arow, g.OC - 1) * K;
+    arow_ok[mi] = arow < g.OC;
+  }
+
+  f32x4 acc[MI][NTW];
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int i = 0; i < NTW; ++i) acc[mi][i] = {0.f, 0.f, 0.f, 0.f};
 
   const int kk = threadIdx.x % CV6_BK;
-  const int nn0 = (threadIdx.x / CV6_BK) * (CV6_BN / 8);
-  ushort breg[CV6_BN / 8];                  // !KM
-  KmRun<CV6_BN / 8> brun;                   // KM
+  const int nn0 = (threadIdx.x / CV6_BK) * NCOL;
+  ushort breg[NCOL];                        // !KM
+  KmRun<NCOL> brun;                         // KM
   const int foff_lo = km_frag_off(lane, 0), foff_hi = km_frag_off(lane, 4);
 
   auto gather = [&](int k0) {
@@ -222,25 +264,25 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v6(
     const int dh = r / 3, dw = r - dh * 3;
     const ushort* plane = xc + (int64_t)ic * planeB;
     if (LG_OW_T >= 4) {
-      // whole 16-col segment inside one output row
+      // whole NCOL-column segment inside one output row
       int n = min(n0 + nn0, N - 1);
       int b = n >> g.lg_ohw;
       int q = n & ((1 << g.lg_ohw) - 1);
       int oh = q >> g.lg_ow;
-      int ow0 = min(q & ((1 << g.lg_ow) - 1), g.OW - CV6_BN / 8);
+      int ow0 = min(q & ((1 << g.lg_ow) - 1), g.OW - NCOL);
       const ushort* row = plane + (int64_t)b * HpWp
                           + (oh * STRIDE + dh) * g.Wp + ow0 * STRIDE + dw;
       if constexpr (KM) {
-        brun.load8(0, row);
-        brun.load8(1, row + 8);
+#pragma unroll
+        for (int j = 0; j < NCOL / 8; ++j) brun.load8(j, row + 8 * j);
       } else {
 #pragma unroll
-        for (int j = 0; j < CV6_BN / 8; ++j) breg[j] = row[j * STRIDE];
+        for (int j = 0; j < NCOL; ++j) breg[j] = row[j * STRIDE];
       }
     } else {
       // OW = 4 or 8: hoist per sub-row of OW columns
       constexpr int SUBW = 1 << LG_OW_T;
-      constexpr int NROW = (CV6_BN / 8) / SUBW;
+      constexpr int NROW = NCOL / SUBW;
 #pragma unroll
       for (int rr = 0; rr < NROW; ++rr) {
         int n = min(n0 + nn0 + rr * SUBW, N - 1);
@@ -261,11 +303,15 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v6(
     }
   };
   auto commit = [&](int buf) {
-    if constexpr (KM) {
+    if constexpr (KM && NCOL == 16) {
       km_store<CV6_BK>(bT_lds[buf], kk, nn0 / 16, brun.v[0], brun.v[1]);
+    } else if constexpr (KM) {
+      // 8 columns: one half of n-tile nn0 / 16
+      km_store_half<CV6_BK>(bT_lds[buf], kk, nn0 / 16, (nn0 / 8) & 1,
+                            brun.v[0]);
     } else {
 #pragma unroll
-      for (int j = 0; j < CV6_BN / 8; ++j)
+      for (int j = 0; j < NCOL; ++j)
         bT_lds[buf][(nn0 + j) * (CV6_BK + CV6_PAD) + kk] = (short)breg[j];
     }
   };
@@ -275,28 +321,34 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v6(
   // the gather alone and the MFMAs never wait for a load issued in their
   // own step (loaded in place, A's wait also drained the gather just
   // issued in front of it).
-  auto load_a = [&](int k0) {
-    return *reinterpret_cast<const uint4*>(wrow + k0 + 8 * (lane >> 4));
+  auto load_a = [&](int mi, int k0) {
+    return *reinterpret_cast<const uint4*>(wrow[mi] + k0 + 8 * (lane >> 4));
   };
   // rows past OC are zeroed at use, so the load is not waited for here
-  auto use_a = [&](uint4 av) {
-    if (!arow_ok) av = make_uint4(0, 0, 0, 0);
+  auto use_a = [&](int mi, uint4 av) {
+    if (!arow_ok[mi]) av = make_uint4(0, 0, 0, 0);
     return __builtin_bit_cast(bf16x8, av);
   };
 
   gather(0);
-  uint4 a_next = load_a(0);
+  uint4 a_next[MI];
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) a_next[mi] = load_a(mi, 0);
   commit(0);
   int cur = 0;
   for (int k0 = 0; k0 < K; k0 += CV6_BK) {
     __syncthreads();
-    const bf16x8 a = use_a(a_next);
+    bf16x8 a[MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) a[mi] = use_a(mi, a_next[mi]);
     if (k0 + CV6_BK < K) {
       gather(k0 + CV6_BK);
-      a_next = load_a(k0 + CV6_BK);
-    }
 #pragma unroll
-    for (int nt = 0; nt < CV6_BN / 16; ++nt) {
+      for (int mi = 0; mi < MI; ++mi) a_next[mi] = load_a(mi, k0 + CV6_BK);
+    }
+    // one B fragment read per n-tile feeds the wave's MI MFMAs
+#pragma unroll
+    for (int nt = 0; nt < NTW; ++nt) {
       bf16x8 b;
       if constexpr (KM)
         b = km_frag<CV6_BK>(bT_lds[cur], foff_lo, foff_hi, nt, 0);
@@ -304,21 +356,27 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v6(
         b = *reinterpret_cast<const bf16x8*>(
             &bT_lds[cur][(nt * 16 + (lane & 15)) * (CV6_BK + CV6_PAD)
                          + 8 * (lane >> 4)]);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nt], 0, 0, 0);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+        acc[mi][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a[mi], b, acc[mi][nt], 0, 0, 0);
     }
     if (k0 + CV6_BK < K) commit(cur ^ 1);
     cur ^= 1;
   }
 
 #pragma unroll
-  for (int nt = 0; nt < CV6_BN / 16; ++nt) {
-    int n = n0 + nt * 16 + (lane & 15);
-    if (n >= N) continue;
+  for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int m = m0 + wave * 16 + (lane >> 4) * 4 + r;
-      if (m < g.OC)
-        yc[(int64_t)m * N + n] = from_f32<__hip_bfloat16>(acc[nt][r]);
+    for (int nt = 0; nt < NTW; ++nt) {
+      int n = n0 + nt * 16 + (lane & 15);
+      if (n >= N) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int m = m0 + wrow0 + mi * 16 + (lane >> 4) * 4 + r;
+        if (m < g.OC)
+          yc[(int64_t)m * N + n] = from_f32<__hip_bfloat16>(acc[mi][nt][r]);
+      }
     }
   }
 }
@@ -455,22 +513,28 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv3x3_fwd_v8(
 // GEMM ladder), with s_setprio(1) around the MFMA cluster (T5).
 // Requires K % 64 == 0 (IC a multiple of 64); launcher falls back to
 // v6 otherwise.  KM as in fwd v6: a thread's 32 columns are two n-tiles,
-// four ds_write_b128.
-template <int LG_OW_T, int STRIDE, bool KM = false>
+// four ds_write_b128.  TILE as in fwd v6: on the 128x64 block a thread
+// gathers 16 columns, one n-tile, in sub-rows of min(OW, 16).
+template <int LG_OW_T, int STRIDE, bool KM = false, int TILE = 0>
 __global__ __launch_bounds__(CONV_THREADS)
 __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v7(
     const __hip_bfloat16* __restrict__ xp, const __hip_bfloat16* __restrict__ w,
     __hip_bfloat16* __restrict__ y, ConvGeom6 g) {
   static_assert(!KM || STRIDE == 1, "k-major staging needs contiguous runs");
   constexpr int BK = 64;
+  static_assert(TILE == 0 || TILE == 1, "64x128 or 128x64");
+  constexpr int BM = TILE ? 128 : CV6_BM, BN = TILE ? 64 : CV6_BN;
+  constexpr int MI = BM / 64;               // 16-row A fragments per wave
+  constexpr int NTW = BN / 16;              // 16-column n-tiles per wave
+  constexpr int NCOL = BN / 4;              // gathered columns per thread
   int c, tile;
   if (!xcd_remap6(blockIdx.x, g.C, g.tiles_m * g.tiles_n, c, tile)) return;
   const int mt = tile / g.tiles_n;
-  const int m0 = mt * CV6_BM;
-  const int n0 = (tile - mt * g.tiles_n) * CV6_BN;
+  const int m0 = mt * BM;
+  const int n0 = (tile - mt * g.tiles_n) * BN;
 
   __shared__ __attribute__((aligned(16))) short
-      bT_lds[2][CV6_BN * (KM ? BK : BK + CV6_PAD)];
+      bT_lds[2][BN * (KM ? BK : BK + CV6_PAD)];
   const int K = g.IC * 9;
   const int N = g.B * g.OH * g.OW;
   const int HpWp = g.Hp * g.Wp;
@@ -482,18 +546,27 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v7(
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int arow = m0 + wave * 16 + (lane & 15);
-  const __hip_bfloat16* wrow = wc + (int64_t)min(arow, g.OC - 1) * K;
-  const bool arow_ok = arow < g.OC;
-
-  f32x4 acc[CV6_BN / 16];
+  // wave w owns rows m0 + 16*MI*w .. and all BN columns
+  const int wrow0 = 16 * MI * wave;
+  const __hip_bfloat16* wrow[MI];
+  bool arow_ok[MI];
 #pragma unroll
-  for (int i = 0; i < CV6_BN / 16; ++i) acc[i] = {0.f, 0.f, 0.f, 0.f};
+  for (int mi = 0; mi < MI; ++mi) {
+    const int arow = m0 + wrow0 + mi * 16 + (lane & 15);
+    wrow[mi] = wc + (int64_t)min(arow, g.OC - 1) * K;
+    arow_ok[mi] = arow < g.OC;
+  }
 
-  const int kk = threadIdx.x & 63;           // staged k-row
-  const int nn0 = (threadIdx.x >> 6) * 32;   // 32 cols per thread
-  ushort breg[32];                           // !KM
-  KmRun<32> brun;                            // KM
+  f32x4 acc[MI][NTW];
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int i = 0; i < NTW; ++i) acc[mi][i] = {0.f, 0.f, 0.f, 0.f};
+
+  const int kk = threadIdx.x & 63;            // staged k-row
+  const int nn0 = (threadIdx.x >> 6) * NCOL;  // NCOL cols per thread
+  ushort breg[NCOL];                          // !KM
+  KmRun<NCOL> brun;                           // KM
   const int foff_lo = km_frag_off(lane, 0), foff_hi = km_frag_off(lane, 4);
 
   auto gather = [&](int k0) {
@@ -501,8 +574,8 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v7(
     const int ic = k / 9, r = k - ic * 9;
     const int dh = r / 3, dw = r - dh * 3;
     const ushort* plane = xc + (int64_t)ic * planeB;
-    constexpr int SUBW = 1 << (LG_OW_T < 5 ? LG_OW_T : 5);
-    constexpr int NROW = 32 / SUBW;
+    constexpr int SUBW = (1 << LG_OW_T) < NCOL ? (1 << LG_OW_T) : NCOL;
+    constexpr int NROW = NCOL / SUBW;
     static_assert(!KM || SUBW >= 8, "k-major runs are whole 8-column loads");
 #pragma unroll
     for (int rr = 0; rr < NROW; ++rr) {
@@ -511,8 +584,9 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v7(
       int q = n & ((1 << g.lg_ohw) - 1);
       int oh = q >> g.lg_ow;
       int ow0 = q & ((1 << g.lg_ow) - 1);
-      if (SUBW < 32) ow0 = 0;                // sub-row segments are aligned
-      else ow0 = min(ow0, g.OW - 32);
+      // sub-row segments are aligned; so is a whole-row run of exactly OW
+      if (SUBW < NCOL || LG_OW_T < 5) ow0 = 0;
+      else ow0 = min(ow0, g.OW - NCOL);
       const ushort* row = plane + (int64_t)b * HpWp
                           + (oh * STRIDE + dh) * g.Wp + ow0 * STRIDE + dw;
       if constexpr (KM) {
@@ -528,44 +602,58 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v7(
   };
   auto commit = [&](int buf) {
     if constexpr (KM) {
-      km_store<BK>(bT_lds[buf], kk, nn0 / 16, brun.v[0], brun.v[1]);
-      km_store<BK>(bT_lds[buf], kk, nn0 / 16 + 1, brun.v[2], brun.v[3]);
+#pragma unroll
+      for (int j = 0; j < NCOL / 16; ++j)
+        km_store<BK>(bT_lds[buf], kk, nn0 / 16 + j, brun.v[2 * j],
+                     brun.v[2 * j + 1]);
     } else {
 #pragma unroll
-      for (int j = 0; j < 32; ++j)
+      for (int j = 0; j < NCOL; ++j)
         bT_lds[buf][(nn0 + j) * (BK + CV6_PAD) + kk] = (short)breg[j];
     }
   };
 
   // A one step ahead and after the gather, as in fwd v6
-  auto load_a = [&](int k0, int sub) {
+  auto load_a = [&](int mi, int k0, int sub) {
     return *reinterpret_cast<const uint4*>(
-        wrow + k0 + sub * 32 + 8 * (lane >> 4));
+        wrow[mi] + k0 + sub * 32 + 8 * (lane >> 4));
   };
   // rows past OC are zeroed at use, so the load is not waited for here
-  auto use_a = [&](uint4 av) {
-    if (!arow_ok) av = make_uint4(0, 0, 0, 0);
+  auto use_a = [&](int mi, uint4 av) {
+    if (!arow_ok[mi]) av = make_uint4(0, 0, 0, 0);
     return __builtin_bit_cast(bf16x8, av);
   };
 
+  struct AStep { uint4 v[MI][2]; };         // [fragment][K half]
   gather(0);
-  uint4 a_next[2] = {load_a(0, 0), load_a(0, 1)};
+  AStep a_next;
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    a_next.v[mi][0] = load_a(mi, 0, 0);
+    a_next.v[mi][1] = load_a(mi, 0, 1);
+  }
   commit(0);
   int cur = 0;
   for (int k0 = 0; k0 < K; k0 += BK) {
     __syncthreads();
-    const uint4 a_cur[2] = {a_next[0], a_next[1]};
+    const AStep a_cur = a_next;
     if (k0 + BK < K) {
       gather(k0 + BK);
-      a_next[0] = load_a(k0 + BK, 0);
-      a_next[1] = load_a(k0 + BK, 1);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) {
+        a_next.v[mi][0] = load_a(mi, k0 + BK, 0);
+        a_next.v[mi][1] = load_a(mi, k0 + BK, 1);
+      }
     }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
-      const bf16x8 a = use_a(a_cur[sub]);
+      bf16x8 a[MI];
 #pragma unroll
-      for (int nt = 0; nt < CV6_BN / 16; ++nt) {
+      for (int mi = 0; mi < MI; ++mi) a[mi] = use_a(mi, a_cur.v[mi][sub]);
+      // one B fragment read per n-tile feeds the wave's MI MFMAs
+#pragma unroll
+      for (int nt = 0; nt < NTW; ++nt) {
         bf16x8 b;
         if constexpr (KM)
           b = km_frag<BK>(bT_lds[cur], foff_lo, foff_hi, nt, sub * 32);
@@ -573,8 +661,10 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v7(
           b = *reinterpret_cast<const bf16x8*>(
               &bT_lds[cur][(nt * 16 + (lane & 15)) * (BK + CV6_PAD)
                            + sub * 32 + 8 * (lane >> 4)]);
-        acc[nt] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nt], 0, 0, 0);
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+          acc[mi][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a[mi], b, acc[mi][nt], 0, 0, 0);
       }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -583,14 +673,17 @@ __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_fwd_v7(
   }
 
 #pragma unroll
-  for (int nt = 0; nt < CV6_BN / 16; ++nt) {
-    int n = n0 + nt * 16 + (lane & 15);
-    if (n >= N) continue;
+  for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int m = m0 + wave * 16 + (lane >> 4) * 4 + r;
-      if (m < g.OC)
-        yc[(int64_t)m * N + n] = from_f32<__hip_bfloat16>(acc[nt][r]);
+    for (int nt = 0; nt < NTW; ++nt) {
+      int n = n0 + nt * 16 + (lane & 15);
+      if (n >= N) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int m = m0 + wrow0 + mi * 16 + (lane >> 4) * 4 + r;
+        if (m < g.OC)
+          yc[(int64_t)m * N + n] = from_f32<__hip_bfloat16>(acc[mi][nt][r]);
+      }
     }
   }
 }
@@ -1560,29 +1653,45 @@ extern "C" const char* ols_conv3x3_staging(int dir, int IC, int OC, int B,
   return conv3_kmajor(dir, IC, OC, B, H, W, stride) ? "kmajor" : "nmajor";
 }
 
+extern "C" const char* ols_conv3x3_tile(int dir, int IC, int OC, int B,
+                                        int H, int W, int stride) {
+  return conv3_tile_name(conv3_tile(dir, IC, OC, B, H, W, stride));
+}
+
 extern "C" void ols_conv3x3_fwd_p(const void* xp, const void* w, void* y,
                                   int C, int IC, int OC, int B, int H, int W,
                                   int stride, hipStream_t stream) {
   ConvGeom6 g;
   fill_geom6(g, C, IC, OC, B, H, W, stride);
-  g.tiles_m = conv3_cdiv(OC, CV6_BM);
-  g.tiles_n = conv3_cdiv(B * g.OH * g.OW, CV6_BN);
   ConvKernel6 k = nullptr;
   const Conv3Route route = conv3_route_fwd_v6(IC, OC, B, H, W, stride);
   const bool km = conv3_kmajor_v6(0, route);
+  const int tile = conv3_tile_v6(route, OC);
+  g.tiles_m = conv3_cdiv(OC, tile ? 128 : CV6_BM);
+  g.tiles_n = conv3_cdiv(B * g.OH * g.OW, tile ? 64 : CV6_BN);
+  // (route, staging, tile) -> instantiation
 #define KM_CASE(id, kern, ...)                                              \
   case id: k = km ? kern<__VA_ARGS__, true> : kern<__VA_ARGS__, false>; break;
+#define TILE_PICK(kern, km_, ...)                                           \
+  (tile ? kern<__VA_ARGS__, km_, 1> : kern<__VA_ARGS__, km_, 0>)
+#define TILE_CASE(id, kern, ...)                                            \
+  case id: k = TILE_PICK(kern, false, __VA_ARGS__); break;
+#define KM_TILE_CASE(id, kern, ...)                                         \
+  case id:                                                                  \
+    k = km ? TILE_PICK(kern, true, __VA_ARGS__)                             \
+           : TILE_PICK(kern, false, __VA_ARGS__);                           \
+    break;
   switch (route) {
-    KM_CASE(CV3_FWD_V6_2_1, k_conv3x3_fwd_v6, 2, 1)
-    KM_CASE(CV3_FWD_V6_3_1, k_conv3x3_fwd_v6, 3, 1)
-    KM_CASE(CV3_FWD_V6_4_1, k_conv3x3_fwd_v6, 4, 1)
-    case CV3_FWD_V6_2_2: k = k_conv3x3_fwd_v6<2, 2>; break;
-    case CV3_FWD_V6_3_2: k = k_conv3x3_fwd_v6<3, 2>; break;
-    case CV3_FWD_V6_4_2: k = k_conv3x3_fwd_v6<4, 2>; break;
+    KM_TILE_CASE(CV3_FWD_V6_2_1, k_conv3x3_fwd_v6, 2, 1)
+    KM_TILE_CASE(CV3_FWD_V6_3_1, k_conv3x3_fwd_v6, 3, 1)
+    KM_TILE_CASE(CV3_FWD_V6_4_1, k_conv3x3_fwd_v6, 4, 1)
+    TILE_CASE(CV3_FWD_V6_2_2, k_conv3x3_fwd_v6, 2, 2)
+    TILE_CASE(CV3_FWD_V6_3_2, k_conv3x3_fwd_v6, 3, 2)
+    TILE_CASE(CV3_FWD_V6_4_2, k_conv3x3_fwd_v6, 4, 2)
     // [n][k] only: measured no faster k-major (conv3_kmajor_v6)
-    case CV3_FWD_V7_3_1: k = k_conv3x3_fwd_v7<3, 1>; break;
-    KM_CASE(CV3_FWD_V7_4_1, k_conv3x3_fwd_v7, 4, 1)
-    KM_CASE(CV3_FWD_V7_5_1, k_conv3x3_fwd_v7, 5, 1)
+    TILE_CASE(CV3_FWD_V7_3_1, k_conv3x3_fwd_v7, 3, 1)
+    KM_TILE_CASE(CV3_FWD_V7_4_1, k_conv3x3_fwd_v7, 4, 1)
+    KM_TILE_CASE(CV3_FWD_V7_5_1, k_conv3x3_fwd_v7, 5, 1)
     case CV3_FWD_V8_2_1: k = k_conv3x3_fwd_v8<2, 1>; break;
     case CV3_FWD_V8_3_1: k = k_conv3x3_fwd_v8<3, 1>; break;
     case CV3_FWD_V8_4_1: k = k_conv3x3_fwd_v8<4, 1>; break;
@@ -1591,6 +1700,9 @@ extern "C" void ols_conv3x3_fwd_p(const void* xp, const void* w, void* y,
     case CV3_FWD_V8_4_2: k = k_conv3x3_fwd_v8<4, 2>; break;
     default: return;                    // not a v6-family fwd route
   }
+#undef TILE_PICK
+#undef TILE_CASE
+#undef KM_TILE_CASE
   launch6(k, xp, w, y, g, stream);
 }
 

@@ -49,14 +49,15 @@ static inline const char* conv3_route_name(Conv3Route r) {
   return names[r];
 }
 
-// The five A/B switches, read on every call.  OLSIM_CONV_V=5 sends every
-// shape to the v5 family; the other four act on presence, whatever the
+// The six A/B switches, read on every call.  OLSIM_CONV_V=5 sends every
+// shape to the v5 family; the other five act on presence, whatever the
 // value (OLSIM_CONV_DW8=0 restores the scalar wgrad gather because it is
 // set): OLSIM_CONV_V8 the two-ahead fwd_v8, OLSIM_CONV_DW64 the BK=64
 // dgrad_v7 / wgrad_v7, OLSIM_CONV_DW8 no run-vectorised wgrad_v8 / v8s,
-// OLSIM_CONV_NMAJOR the [n][k] B tile in every fwd / dgrad kernel.
+// OLSIM_CONV_NMAJOR the [n][k] B tile in every fwd / dgrad kernel,
+// OLSIM_CONV_BM64 the 64x128 block tile in every forward kernel.
 struct Conv3Env {
-  bool v5, v8, dw64, no_dw8, nmajor;
+  bool v5, v8, dw64, no_dw8, nmajor, bm64;
 };
 
 static inline Conv3Env conv3_env() {
@@ -65,7 +66,8 @@ static inline Conv3Env conv3_env() {
           getenv("OLSIM_CONV_V8") != nullptr,
           getenv("OLSIM_CONV_DW64") != nullptr,
           getenv("OLSIM_CONV_DW8") != nullptr,
-          getenv("OLSIM_CONV_NMAJOR") != nullptr};
+          getenv("OLSIM_CONV_NMAJOR") != nullptr,
+          getenv("OLSIM_CONV_BM64") != nullptr};
 }
 
 static inline int conv3_cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -190,6 +192,8 @@ static inline Conv3Route conv3_route_wgrad_v6(int IC, int OC, int B, int H,
 // fwd_v7<3,1> (OW = 8, the 256-channel stage) stays [n][k]: k-major
 // measured 1.3 % slower there (0.850 vs 0.839 ms at C=250,
 // profiles/conv_kmajor_r06.md), so it has no k-major instantiation.
+// Re-measured on the 128x64 tile, where it commits half as many 2-byte
+// stores: 0.777 ms either way (profiles/conv_tile_r08.md), so still none.
 static inline bool conv3_kmajor_v6(int dir, Conv3Route r) {
   if (conv3_env().nmajor) return false;
   if (dir == 0)
@@ -198,6 +202,39 @@ static inline bool conv3_kmajor_v6(int dir, Conv3Route r) {
   if (dir == 1)
     return r == CV3_DGRAD_V6_2 || r == CV3_DGRAD_V6_3 || r == CV3_DGRAD_V6_4;
   return false;
+}
+
+// Block tile of a v6-family forward route: 0 = 64x128 (four waves of 16
+// rows x 128 columns), 1 = 128x64 (four waves of 32 rows x 64 columns, each
+// B fragment read feeding two MFMAs, half the gather and half the B commits
+// per MFMA).  Like the staging, one more template argument that the route
+// name does not carry.  fwd_v6<*,1>, fwd_v6<*,2> and fwd_v7<*,1> take the
+// taller tile when it adds no padded rows (OC = 96, 128, 256, 512 ...; not
+// 64 or 192); fwd_v8 is a record kept as measured, and the dgrad / wgrad
+// kernels have the one tile.  The flipped-weight dgrad runs the forward of
+// (OC, IC) and so gets that forward's tile.
+// All nine instantiations measured faster on the taller tile (C=250, B=16,
+// OLSIM_CONV_BM64 set against unset, profiles/conv_tile_r08.md): stride 2
+// +30 %, fwd_v7<3,1> +7.2 %, fwd_v7<4,1> +4.7 %, fwd_v7<5,1> +3.8 %,
+// fwd_v6<2,1> +2.9 %, fwd_v6<3,1> / <4,1> +16 / +5.5 % off the flagship;
+// none is gated back.  Where it does not fit (OC = 64), the same 32x64
+// wave tile as a 2x2 wave grid inside the 64x128 block measured 10-25 %
+// slower (the two waves of a row pair load the same A) and is not built.
+static inline int conv3_tile_v6(Conv3Route r, int OC) {
+  if (conv3_env().bm64) return 0;
+  if (conv3_cdiv(OC, 128) * 128 != conv3_cdiv(OC, 64) * 64) return 0;
+  switch (r) {
+    case CV3_FWD_V6_2_1: case CV3_FWD_V6_3_1: case CV3_FWD_V6_4_1:
+    case CV3_FWD_V6_2_2: case CV3_FWD_V6_3_2: case CV3_FWD_V6_4_2:
+    case CV3_FWD_V7_3_1: case CV3_FWD_V7_4_1: case CV3_FWD_V7_5_1:
+      return 1;
+    default:
+      return 0;
+  }
+}
+
+static inline const char* conv3_tile_name(int tile) {
+  return tile == 1 ? "128x64" : "64x128";
 }
 
 // dir: 0 fwd, 1 dgrad, 2 wgrad.  Includes the family decision the Python
@@ -221,4 +258,11 @@ static inline Conv3Route conv3_route(int dir, int IC, int OC, int B, int H,
 static inline bool conv3_kmajor(int dir, int IC, int OC, int B, int H, int W,
                                 int stride) {
   return conv3_kmajor_v6(dir, conv3_route(dir, IC, OC, B, H, W, stride));
+}
+
+// block tile of the kernel conv3_route() names for the shape
+static inline int conv3_tile(int dir, int IC, int OC, int B, int H, int W,
+                             int stride) {
+  if (dir != 0) return 0;
+  return conv3_tile_v6(conv3_route(dir, IC, OC, B, H, W, stride), OC);
 }

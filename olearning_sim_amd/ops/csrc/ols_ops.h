@@ -54,6 +54,9 @@ extern "C" const char* ols_conv3x3_route(int dir, int IC, int OC, int B,
 // "kmajor" or "nmajor": the B-tile staging of the kernel that route runs
 extern "C" const char* ols_conv3x3_staging(int dir, int IC, int OC, int B,
                                            int H, int W, int stride);
+// "64x128" or "128x64": the block tile of the kernel that route runs
+extern "C" const char* ols_conv3x3_tile(int dir, int IC, int OC, int B,
+                                        int H, int W, int stride);
 extern "C" void ols_conv3x3_fwd_p(const void* xp, const void* w, void* y,
                                   int C, int IC, int OC, int B, int H, int W,
                                   int stride, hipStream_t stream);
