@@ -27,6 +27,16 @@ class EngineJob:
     lr: float = 0.05
     prox_mu: float = 0.0            # FedProx proximal coefficient (0 = FedAvg)
 
+    # server-side update rule: each client's update is scaled to L2 norm
+    # <= clip_norm before it is aggregated (0 = off); N(0, sigma^2) with
+    # sigma = noise_multiplier * clip_norm / total_weight is then added to
+    # every master coordinate (the DP-FedAvg mechanism; no (eps, delta)
+    # accounting).  update_norm_stats records the clients' update norms
+    # per round without clipping them.
+    clip_norm: float = 0.0
+    noise_multiplier: float = 0.0
+    update_norm_stats: bool = False
+
     # execution
     dtype: str = "float32"          # compute dtype of client replicas
     device: str = "cpu"

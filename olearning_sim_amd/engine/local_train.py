@@ -16,7 +16,7 @@ After the E steps, ONE weighted-delta reduction kernel folds
 
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Any, Dict, Optional
 
 import torch
 
@@ -30,9 +30,15 @@ class LocalTrainer:
     def __init__(self, model: ClientBatchedModel, master: FlatParams,
                  data: SyntheticFederatedData, lr: float, prox_mu: float,
                  local_steps: int, batch_size: int, dtype: torch.dtype,
-                 report_loss: bool = True):
+                 report_loss: bool = True, clip_norm: float = 0.0,
+                 update_norm_stats: bool = False):
         # report_loss=False avoids a device sync per chunk (bench path)
         self.report_loss = report_loss
+        # clip_norm > 0: each client's update is scaled to norm <= clip_norm
+        # in the aggregation; update_norm_stats: the norms are computed and
+        # returned even when nothing is clipped
+        self.clip_norm = clip_norm
+        self.update_norm_stats = update_norm_stats
         self.model = model
         self.master = master
         self.data = data
@@ -82,12 +88,16 @@ class LocalTrainer:
 
     def train_chunk(self, client_ids: torch.Tensor, weights: torch.Tensor,
                     round_idx: int, delta_flat: torch.Tensor,
-                    wsum: Optional[float] = None) -> Dict[str, float]:
+                    wsum: Optional[float] = None) -> Dict[str, Any]:
         """Train one chunk of clients; accumulate weighted deltas.
 
         client_ids: [C] int64; weights: [C] fp32 aggregation weights
         (0 for clients whose gradient the behaviour model drops);
         delta_flat: fp32 [P] accumulator with the master's layout.
+
+        With clipping or norm statistics on, the result also carries "sq"
+        (fp32 [C], each client's squared update norm) and "weights", both
+        on the device and not read here.
         """
         C = int(client_ids.numel())
         cast = self._cast_params()
@@ -115,9 +125,19 @@ class LocalTrainer:
             if self.report_loss and step == self.local_steps - 1:
                 last_loss = float(loss.detach())
             del grads
+        out: Dict[str, Any] = {"loss": last_loss, "clients": C}
         with torch.no_grad():
             delta_views = list(self.master.views_of(delta_flat).values())
+            final = [p.detach() for p in plist]
+            if self.clip_norm > 0.0 or self.update_norm_stats:
+                sq = fused.client_delta_sqnorm(final, glist)
+                out["sq"], out["weights"] = sq, weights
+                if self.clip_norm > 0.0:
+                    # s_c = min(1, S/||delta_c||) folds into the weights;
+                    # their sum stays on the device for the accumulate
+                    weights, wsum = fused.clip_weights(sq, weights,
+                                                       self.clip_norm)
             fused.weighted_delta_accum(
-                delta_views, [p.detach() for p in plist], glist, weights,
+                delta_views, final, glist, weights,
                 wsum=wsum if wsum is not None else float(weights.sum()))
-        return {"loss": last_loss, "clients": C}
+        return out

@@ -56,6 +56,12 @@ class LogicalEngine:
         self.device = torch.device(self.ctx.device if dist_ctx else job.device)
         self.dtype = job.torch_dtype()
         self.result_sink = result_sink
+        if job.clip_norm < 0 or job.noise_multiplier < 0:
+            raise ValueError("clip_norm and noise_multiplier must be >= 0")
+        if job.noise_multiplier > 0 and not job.clip_norm > 0:
+            # the noise scale is a multiple of the clip norm: without a
+            # bound on the updates there is nothing to calibrate it to
+            raise ValueError("noise_multiplier needs clip_norm > 0")
         self.stop_requested = False
 
         self.model = build_model(job.model_name, **job.model_kwargs)
@@ -78,7 +84,8 @@ class LogicalEngine:
             self.model, self.master, self.data, lr=job.lr,
             prox_mu=job.prox_mu, local_steps=job.local_steps,
             batch_size=job.batch_size, dtype=self.dtype,
-            report_loss=result_sink is not None)
+            report_loss=result_sink is not None, clip_norm=job.clip_norm,
+            update_norm_stats=job.update_norm_stats)
         if behavior is None and job.behavior_strategy:
             from ..deviceflow.sampler import BehaviorSampler
             behavior = BehaviorSampler(job.behavior_strategy,
@@ -101,7 +108,8 @@ class LogicalEngine:
         # hidden (SURVEY §5 "overlap the collective")
         self._delta = self.master.zeros_like_flat()
         self._delta_alt: Optional[torch.Tensor] = None
-        self._pending_agg = None     # (work, delta_buf, total_weight)
+        # (work, delta_buf, total_weight, round_idx)
+        self._pending_agg = None
         # totals across rounds (reference logical_result accounting)
         self.success_total = 0
         self.failed_total = 0
@@ -203,12 +211,46 @@ class LogicalEngine:
         master (called wherever the master is next read)."""
         if self._pending_agg is None:
             return
-        work, delta, total_weight = self._pending_agg
+        work, delta, total_weight, round_idx = self._pending_agg
         self._pending_agg = None
         if work is not None:
             work.wait()
         if total_weight > 0:
             fused.apply_aggregate([self.master.flat], [delta], total_weight)
+            self._add_noise(round_idx, total_weight)
+
+    def _add_noise(self, round_idx: int, total_weight: float) -> None:
+        """master += N(0, sigma^2) per coordinate, sigma = noise_multiplier
+        * clip_norm / total_weight: the Gaussian mechanism on the clipped
+        mean.  The generator is seeded from (job.seed, round_idx) and not
+        from the rank, so every rank adds the same tensor and the masters
+        stay equal, and a resumed run draws the noise it would have drawn."""
+        job = self.job
+        if job.noise_multiplier <= 0 or total_weight <= 0:
+            return
+        sigma = job.noise_multiplier * job.clip_norm / total_weight
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed((job.seed * 1_000_003 + round_idx * 7919 + 0x5EED)
+                        % (2 ** 63))
+        noise = torch.randn(self.master.flat.shape, generator=gen,
+                            device=self.device, dtype=self.master.flat.dtype)
+        self.master.flat.add_(noise, alpha=sigma)
+
+    def _update_norm_counts(self, chunks) -> List[float]:
+        """[clipped, sum of norms, clients] over this rank's clients of
+        weight > 0 (dropped clients and tail padding carry weight 0), from
+        the chunks' device-side (sq, weights): the round's one host read."""
+        sq = torch.cat([c[0] for c in chunks])
+        live = torch.cat([c[1] for c in chunks]) > 0
+        if self.job.clip_norm > 0:
+            S = torch.tensor(self.job.clip_norm, dtype=torch.float32,
+                             device=sq.device)
+            clipped = (live & (sq > S * S)).sum()
+        else:
+            clipped = torch.zeros((), dtype=torch.int64, device=sq.device)
+        norms = torch.where(live, sq.sqrt(), torch.zeros_like(sq))
+        return torch.stack([clipped.double(), norms.double().sum(),
+                            live.sum().double()]).tolist()
 
     def _op_train(self, round_idx: int,
                   op_name: str = "train") -> Dict[str, Any]:
@@ -237,6 +279,7 @@ class LogicalEngine:
         self._delta.zero_()
         weights_all = (~active_drop).float()
         losses: List[float] = []
+        norm_chunks = []            # (sq, weights) per chunk, on the device
         trained = 0
         n_active = int(active_ids.numel())
         # chunk size derives from the FIXED cohort, not this round's
@@ -261,6 +304,8 @@ class LogicalEngine:
             trained += min(stats["clients"], n_active - lo)
             if stats["loss"]:
                 losses.append(stats["loss"])
+            if "sq" in stats:
+                norm_chunks.append((stats["sq"], stats["weights"]))
             if flow_id is not None:
                 # per-chunk summary into the gradient house (the per-
                 # client tensors aggregate in-engine; the message plane
@@ -271,6 +316,10 @@ class LogicalEngine:
                                                  "loss": stats["loss"]})
 
         local_weight = float(weights_all.sum())
+        want_norms = job.clip_norm > 0 or job.update_norm_stats
+        norm_counts = [0.0, 0.0, 0.0]
+        if want_norms and norm_chunks:
+            norm_counts = self._update_norm_counts(norm_chunks)
         # per-tier success/failed (client ids map to tiers by prefix range)
         T = len(self.tier_names)
         succ_t = [0] * T
@@ -286,20 +335,24 @@ class LogicalEngine:
         # cross-GPU aggregation: one RCCL all-reduce of the flat delta +
         # one small all-reduce carrying (weight, per-tier succ/fail)
         if self.ctx.enabled:
-            stats = torch.tensor([local_weight] + succ_t + fail_t,
+            stats = torch.tensor([local_weight] + succ_t + fail_t
+                                 + (norm_counts if want_norms else []),
                                  dtype=torch.float64, device=self.device)
             work = pdist.all_reduce_flat(self._delta, async_op=True)
             pdist.all_reduce_flat(stats)      # small, waited (round status)
             total_weight = float(stats[0])
             succ_t = [int(x) for x in stats[1:1 + T]]
             fail_t = [int(x) for x in stats[1 + T:1 + 2 * T]]
+            if want_norms:
+                norm_counts = [float(x) for x in stats[1 + 2 * T:]]
             success = sum(succ_t)
             failed = sum(fail_t)
             # defer the big delta wait+apply: the collective overlaps
             # everything until the master is next read; swap to the
             # alternate delta buffer so the next round's accumulation
             # never races the in-flight reduce
-            self._pending_agg = (work, self._delta, total_weight)
+            self._pending_agg = (work, self._delta, total_weight,
+                                 round_idx)
             if self._delta_alt is None:
                 self._delta_alt = self.master.zeros_like_flat()
             self._delta, self._delta_alt = self._delta_alt, self._delta
@@ -309,6 +362,7 @@ class LogicalEngine:
             if total_weight > 0:
                 fused.apply_aggregate([self.master.flat], [self._delta],
                                       total_weight)
+                self._add_noise(round_idx, total_weight)
 
         self.success_total += success
         self.failed_total += failed
@@ -324,7 +378,7 @@ class LogicalEngine:
         # failed > dynamic_nums; job.dynamic_num sums across all
         # data/tiers and would inflate the single-segment tolerance)
         round_failed = any(f > d for f, d in zip(fail_t, dyn))
-        return {
+        record = {
             "success": success,
             "failed": failed,
             "success_per_tier": succ_t,
@@ -333,6 +387,14 @@ class LogicalEngine:
             "loss": sum(losses) / len(losses) if losses else None,
             "round_failed": round_failed,
         }
+        if want_norms:
+            n_clipped, norm_sum, n_live = norm_counts
+            record["clipped"] = int(n_clipped)
+            record["update_norm_mean"] = (norm_sum / n_live if n_live > 0
+                                          else None)
+            record["clipped_frac"] = (n_clipped / n_live if n_live > 0
+                                      else 0.0)
+        return record
 
     def _op_script(self, round_idx: int, name: str) -> Dict[str, Any]:
         """User script-file operator: sharded subprocess execution of
@@ -419,6 +481,9 @@ class LogicalEngine:
             if "eval_acc" in record:
                 self.perf.record(job.task_id, "eval_acc",
                                  record["eval_acc"], round_idx)
+            if "clipped_frac" in record:
+                self.perf.record(job.task_id, "clipped_frac",
+                                 record["clipped_frac"], round_idx)
         if job.save_every_round and job.checkpoint_dir                 and "checkpoint" not in record:
             self._finish_aggregate()
             if self.ctx.rank == 0:

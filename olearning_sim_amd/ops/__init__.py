@@ -12,11 +12,14 @@ from .fused import (
     load_hip_ops,
     fused_sgd_update,
     weighted_delta_accum,
+    client_delta_sqnorm,
+    clip_weights,
     apply_aggregate,
     cross_entropy_fwd_bwd,
 )
 
 __all__ = [
     "hip_ops_available", "load_hip_ops", "fused_sgd_update",
-    "weighted_delta_accum", "apply_aggregate", "cross_entropy_fwd_bwd",
+    "weighted_delta_accum", "client_delta_sqnorm", "clip_weights",
+    "apply_aggregate", "cross_entropy_fwd_bwd",
 ]

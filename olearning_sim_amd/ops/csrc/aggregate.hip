@@ -11,6 +11,10 @@
 // of the c-loop is a fully coalesced stream; client weights are staged
 // in LDS once per workgroup.  fp32 accumulation regardless of the
 // replica dtype.
+//
+// W comes from the host as a float, or, when wsum_dev is not null, from
+// one float on the device (clip.hip k_clip_weights writes it there, so
+// clipped aggregation needs no host round trip per chunk).
 
 #include "common.h"
 #include "ols_ops.h"
@@ -22,7 +26,9 @@ __global__ __launch_bounds__(OLS_THREADS) void k_delta_accum(
     float* __restrict__ delta, const T* __restrict__ buf,
     const T* __restrict__ master, const float* __restrict__ weights,
     const int64_t* __restrict__ offs, int nblocks, int64_t clients,
-    int64_t pglobal, float wsum) {
+    int64_t pglobal, float wsum_host,
+    const float* __restrict__ wsum_dev) {
+  const float wsum = wsum_dev ? *wsum_dev : wsum_host;
   __shared__ float w_lds[MAX_LDS_W];
   const bool w_in_lds = clients <= MAX_LDS_W;
   if (w_in_lds) {
@@ -55,7 +61,9 @@ template <typename T>
 __global__ __launch_bounds__(OLS_THREADS) void k_delta_accum_v8(
     float* __restrict__ delta, const T* __restrict__ buf,
     const T* __restrict__ master, const float* __restrict__ weights,
-    int64_t clients, int64_t n, float wsum) {
+    int64_t clients, int64_t n, float wsum_host,
+    const float* __restrict__ wsum_dev) {
+  const float wsum = wsum_dev ? *wsum_dev : wsum_host;
   __shared__ float w_lds[MAX_LDS_W];
   const bool w_in_lds = clients <= MAX_LDS_W;
   if (w_in_lds) {
@@ -95,7 +103,9 @@ template <typename T>
 __global__ __launch_bounds__(OLS_THREADS) void k_delta_accum_cpar(
     float* __restrict__ delta, const T* __restrict__ buf,
     const T* __restrict__ master, const float* __restrict__ weights,
-    int64_t clients, int64_t n, float wsum, int ctile) {
+    int64_t clients, int64_t n, float wsum_host,
+    const float* __restrict__ wsum_dev, int ctile) {
+  const float wsum = wsum_dev ? *wsum_dev : wsum_host;
   const int64_t nv = n / 8;
   const int64_t j8 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
   if (j8 >= nv) return;
@@ -127,7 +137,9 @@ template <typename T>
 __global__ __launch_bounds__(OLS_THREADS) void k_delta_accum_cpar_s(
     float* __restrict__ delta, const T* __restrict__ buf,
     const T* __restrict__ master, const float* __restrict__ weights,
-    int64_t clients, int64_t n, float wsum, int ctile) {
+    int64_t clients, int64_t n, float wsum_host,
+    const float* __restrict__ wsum_dev, int ctile) {
+  const float wsum = wsum_dev ? *wsum_dev : wsum_host;
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const int64_t c0 = (int64_t)blockIdx.y * ctile;
@@ -142,7 +154,7 @@ __global__ __launch_bounds__(OLS_THREADS) void k_delta_accum_cpar_s(
 extern "C" void ols_weighted_delta_accum_flat(
     float* delta, const void* buf, const void* master, const float* weights,
     const int64_t* offs, int nblocks, int64_t clients, int64_t pglobal,
-    float wsum, int dtype, hipStream_t stream) {
+    float wsum, const float* wsum_dev, int dtype, hipStream_t stream) {
   dim3 block(OLS_THREADS);
   if (nblocks == 1 && pglobal % 8 != 0 && dtype == 1 &&
       pglobal < 131072 && clients >= 64) {
@@ -152,7 +164,7 @@ extern "C" void ols_weighted_delta_accum_flat(
     hipLaunchKernelGGL((k_delta_accum_cpar_s<__hip_bfloat16>), grid, block,
                        0, stream, delta, (const __hip_bfloat16*)buf,
                        (const __hip_bfloat16*)master, weights, clients,
-                       pglobal, wsum, ctile);
+                       pglobal, wsum, wsum_dev, ctile);
     return;
   }
   if (nblocks == 1 && pglobal % 8 == 0 && dtype == 1 &&
@@ -165,7 +177,7 @@ extern "C" void ols_weighted_delta_accum_flat(
     hipLaunchKernelGGL((k_delta_accum_cpar<__hip_bfloat16>), grid, block, 0,
                        stream, delta, (const __hip_bfloat16*)buf,
                        (const __hip_bfloat16*)master, weights, clients,
-                       pglobal, wsum, ctile);
+                       pglobal, wsum, wsum_dev, ctile);
     return;
   }
   if (nblocks == 1 && pglobal % 8 == 0 && dtype != 0) {
@@ -174,11 +186,11 @@ extern "C" void ols_weighted_delta_accum_flat(
       hipLaunchKernelGGL((k_delta_accum_v8<__hip_bfloat16>), grid, block, 0,
                          stream, delta, (const __hip_bfloat16*)buf,
                          (const __hip_bfloat16*)master, weights, clients,
-                         pglobal, wsum);
+                         pglobal, wsum, wsum_dev);
     else
       hipLaunchKernelGGL((k_delta_accum_v8<__half>), grid, block, 0, stream,
                          delta, (const __half*)buf, (const __half*)master,
-                         weights, clients, pglobal, wsum);
+                         weights, clients, pglobal, wsum, wsum_dev);
     return;
   }
   dim3 grid(ols_grid(pglobal, OLS_THREADS));
@@ -186,17 +198,19 @@ extern "C" void ols_weighted_delta_accum_flat(
     case 0:
       hipLaunchKernelGGL((k_delta_accum<float>), grid, block, 0, stream,
                          delta, (const float*)buf, (const float*)master,
-                         weights, offs, nblocks, clients, pglobal, wsum);
+                         weights, offs, nblocks, clients, pglobal, wsum,
+                         wsum_dev);
       break;
     case 1:
       hipLaunchKernelGGL((k_delta_accum<__hip_bfloat16>), grid, block, 0,
                          stream, delta, (const __hip_bfloat16*)buf,
                          (const __hip_bfloat16*)master, weights, offs,
-                         nblocks, clients, pglobal, wsum);
+                         nblocks, clients, pglobal, wsum, wsum_dev);
       break;
     default:
       hipLaunchKernelGGL((k_delta_accum<__half>), grid, block, 0, stream,
                          delta, (const __half*)buf, (const __half*)master,
-                         weights, offs, nblocks, clients, pglobal, wsum);
+                         weights, offs, nblocks, clients, pglobal, wsum,
+                         wsum_dev);
   }
 }

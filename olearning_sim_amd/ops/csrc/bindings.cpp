@@ -39,10 +39,11 @@ void fused_sgd_update_flat(at::Tensor buf, at::Tensor grad,
       (float)lr, (float)mu, dtype_code(buf), stream.stream());
 }
 
-void weighted_delta_accum_flat(at::Tensor delta, at::Tensor buf,
-                               at::Tensor global_flat, at::Tensor weights,
-                               at::Tensor offsets, int64_t clients,
-                               double wsum) {
+// wsum_dev: null, or one float on the device that replaces wsum
+void delta_accum_impl(at::Tensor& delta, at::Tensor& buf,
+                      at::Tensor& global_flat, at::Tensor& weights,
+                      at::Tensor& offsets, int64_t clients, double wsum,
+                      const float* wsum_dev) {
   TORCH_CHECK(delta.is_cuda() && delta.scalar_type() == at::kFloat &&
               delta.is_contiguous());
   TORCH_CHECK(buf.is_contiguous() && global_flat.is_contiguous());
@@ -55,7 +56,103 @@ void weighted_delta_accum_flat(at::Tensor delta, at::Tensor buf,
       delta.data_ptr<float>(), buf.data_ptr(), global_flat.data_ptr(),
       weights.data_ptr<float>(), offsets.data_ptr<int64_t>(),
       (int)(offsets.numel() - 1), clients, global_flat.numel(), (float)wsum,
-      dtype_code(buf), stream.stream());
+      wsum_dev, dtype_code(buf), stream.stream());
+}
+
+void weighted_delta_accum_flat(at::Tensor delta, at::Tensor buf,
+                               at::Tensor global_flat, at::Tensor weights,
+                               at::Tensor offsets, int64_t clients,
+                               double wsum) {
+  delta_accum_impl(delta, buf, global_flat, weights, offsets, clients, wsum,
+                   nullptr);
+}
+
+// the same reduction with sum_c w_c read from the device (clip_weights'
+// wsum_eff): no host round trip between the two
+void weighted_delta_accum_flat_dw(at::Tensor delta, at::Tensor buf,
+                                  at::Tensor global_flat, at::Tensor weights,
+                                  at::Tensor offsets, int64_t clients,
+                                  at::Tensor wsum) {
+  TORCH_CHECK(wsum.is_cuda() && wsum.device() == delta.device() &&
+                  wsum.scalar_type() == at::kFloat && wsum.numel() == 1,
+              "weighted_delta_accum_flat_dw: wsum must be one fp32 on the "
+              "GPU of delta");
+  TORCH_CHECK(weights.is_cuda() && weights.is_contiguous());
+  delta_accum_impl(delta, buf, global_flat, weights, offsets, clients, 0.0,
+                   wsum.data_ptr<float>());
+}
+
+// ---- per-client update clipping (clip.hip) ------------------------------
+
+// 16 / itemsize when every row of buf [clients, n] and master start on a
+// 16-byte boundary and n is a whole number of 16-byte packs, else 1
+int sqnorm_vec(const at::Tensor& buf, const at::Tensor& master, int64_t n) {
+  const int v = 16 / (int)buf.element_size();
+  const bool aligned =
+      n % v == 0 &&
+      reinterpret_cast<uintptr_t>(buf.data_ptr()) % 16 == 0 &&
+      reinterpret_cast<uintptr_t>(master.data_ptr()) % 16 == 0;
+  return aligned ? v : 1;
+}
+
+// sq[c] += sum_j (f32(buf[c,j]) - f32(master[j]))^2, deterministic
+void client_delta_sqnorm(at::Tensor sq, at::Tensor buf, at::Tensor master,
+                         int64_t clients) {
+  TORCH_CHECK(sq.is_cuda() && sq.scalar_type() == at::kFloat &&
+                  sq.is_contiguous() && sq.numel() == clients,
+              "client_delta_sqnorm: sq must be contiguous fp32 [clients] on "
+              "the GPU");
+  TORCH_CHECK(buf.is_cuda() && master.is_cuda() &&
+                  buf.device() == sq.device() &&
+                  master.device() == sq.device() && buf.is_contiguous() &&
+                  master.is_contiguous() &&
+                  buf.scalar_type() == master.scalar_type(),
+              "client_delta_sqnorm: buf and master must be contiguous, of "
+              "one dtype, on the GPU of sq");
+  // clients is the grid's y dimension
+  TORCH_CHECK(clients >= 1 && clients <= 65535,
+              "client_delta_sqnorm: clients ", clients, " outside 1..65535");
+  const int64_t n = master.numel();
+  TORCH_CHECK(buf.numel() == clients * n, "client_delta_sqnorm: buf has ",
+              buf.numel(), " elements, expected ", clients, " x ", n);
+  const int dt = dtype_code(buf);
+  if (n == 0) return;
+  const int vec = sqnorm_vec(buf, master, n);
+  const int tiles = ols_sqnorm_tiles(n, clients, vec);
+  at::Tensor part;
+  if (tiles > 1) part = at::empty({clients * tiles}, sq.options());
+  ols_client_delta_sqnorm(sq.data_ptr<float>(),
+                          tiles > 1 ? part.data_ptr<float>() : nullptr,
+                          buf.data_ptr(), master.data_ptr(), clients, n, vec,
+                          dt, at::cuda::getCurrentCUDAStream().stream());
+}
+
+// tiles one client's row of n elements is split over (vec: 1 for the
+// scalar path, 16 / itemsize for the vector path)
+int64_t sqnorm_tiles(int64_t n, int64_t clients, int64_t vec) {
+  TORCH_CHECK(n >= 1 && clients >= 1 && vec >= 1);
+  return ols_sqnorm_tiles(n, clients, (int)vec);
+}
+
+std::tuple<at::Tensor, at::Tensor> clip_weights(at::Tensor sq,
+                                                at::Tensor weights,
+                                                double clip_norm) {
+  TORCH_CHECK(sq.is_cuda() && weights.is_cuda() &&
+                  sq.device() == weights.device() &&
+                  sq.scalar_type() == at::kFloat &&
+                  weights.scalar_type() == at::kFloat &&
+                  sq.is_contiguous() && weights.is_contiguous() &&
+                  sq.dim() == 1 && sq.sizes() == weights.sizes(),
+              "clip_weights: sq and weights must be contiguous fp32 [C] on "
+              "one GPU");
+  TORCH_CHECK(clip_norm > 0.0, "clip_weights: clip_norm must be positive");
+  auto w_eff = at::empty_like(weights);
+  auto wsum_eff = at::empty({1}, weights.options());
+  ols_clip_weights(sq.data_ptr<float>(), weights.data_ptr<float>(),
+                   w_eff.data_ptr<float>(), wsum_eff.data_ptr<float>(),
+                   sq.numel(), (float)clip_norm,
+                   at::cuda::getCurrentCUDAStream().stream());
+  return {w_eff, wsum_eff};
 }
 
 std::tuple<at::Tensor, at::Tensor> cross_entropy_fwd_bwd(at::Tensor logits,
@@ -767,6 +864,14 @@ TORCH_LIBRARY(olsim_hip, m) {
         "Tensor offsets, int clients, float lr, float mu) -> ()");
   m.def("weighted_delta_accum_flat(Tensor(a!) delta, Tensor buf, "
         "Tensor global_flat, Tensor weights, Tensor offsets, int clients, float wsum) -> ()");
+  m.def("weighted_delta_accum_flat_dw(Tensor(a!) delta, Tensor buf, "
+        "Tensor global_flat, Tensor weights, Tensor offsets, int clients, "
+        "Tensor wsum) -> ()");
+  m.def("client_delta_sqnorm(Tensor(a!) sq, Tensor buf, Tensor master, "
+        "int clients) -> ()");
+  m.def("sqnorm_tiles(int n, int clients, int vec) -> int", &sqnorm_tiles);
+  m.def("clip_weights(Tensor sq, Tensor weights, float clip_norm) -> "
+        "(Tensor, Tensor)");
   m.def("cross_entropy_fwd_bwd(Tensor logits, Tensor labels) -> (Tensor, Tensor)");
   m.def("groupnorm_fwd(Tensor x, Tensor res, Tensor gamma, Tensor beta, "
         "int clients, int groups, float eps, bool relu) -> (Tensor, Tensor, Tensor)");
@@ -819,6 +924,9 @@ TORCH_LIBRARY(olsim_hip, m) {
 TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("fused_sgd_update_flat", &fused_sgd_update_flat);
   m.impl("weighted_delta_accum_flat", &weighted_delta_accum_flat);
+  m.impl("weighted_delta_accum_flat_dw", &weighted_delta_accum_flat_dw);
+  m.impl("client_delta_sqnorm", &client_delta_sqnorm);
+  m.impl("clip_weights", &clip_weights);
   m.impl("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.impl("groupnorm_fwd", &groupnorm_fwd);
   m.impl("groupnorm_bwd", &groupnorm_bwd);

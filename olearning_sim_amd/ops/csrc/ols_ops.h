@@ -20,7 +20,18 @@ extern "C" void ols_fused_sgd_update_flat(
 extern "C" void ols_weighted_delta_accum_flat(
     float* delta, const void* buf, const void* master, const float* weights,
     const int64_t* offs, int nblocks, int64_t clients, int64_t pglobal,
-    float wsum, int dtype, hipStream_t stream);
+    float wsum, const float* wsum_dev, int dtype, hipStream_t stream);
+
+// clip.hip: per-client squared update norm and clipped aggregation weights
+extern "C" int ols_sqnorm_tiles(int64_t n, int64_t clients, int vec);
+extern "C" void ols_client_delta_sqnorm(float* sq, float* part,
+                                        const void* buf, const void* master,
+                                        int64_t clients, int64_t n, int vec,
+                                        int dtype, hipStream_t stream);
+extern "C" void ols_clip_weights(const float* sq, const float* weights,
+                                 float* w_eff, float* wsum_eff,
+                                 int64_t clients, float clip,
+                                 hipStream_t stream);
 
 extern "C" void ols_cross_entropy_fwd_bwd(
     const void* logits, const int64_t* labels, float* loss, void* dlogits,

@@ -19,7 +19,7 @@ run here.  A CUDA tensor with no extension raises (no silent fallback).
 from __future__ import annotations
 
 import os
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Union
 
 import torch
 
@@ -139,8 +139,13 @@ def weighted_delta_accum(delta: Sequence[torch.Tensor],
                          client_params: Sequence[torch.Tensor],
                          global_params: Sequence[torch.Tensor],
                          weights: torch.Tensor,
-                         wsum: Optional[float] = None) -> None:
-    """delta[i] (fp32, shape [...]) += sum_c weights[c] * (client_params[i][c] - global[i])."""
+                         wsum: Union[float, torch.Tensor, None] = None
+                         ) -> None:
+    """delta[i] (fp32, shape [...]) += sum_c weights[c] * (client_params[i][c] - global[i]).
+
+    wsum: sum of the weights as a host float, or as a one-element fp32
+    device tensor (clip_weights' wsum_eff), which the kernels read on the
+    device."""
     if not delta:
         return
     if client_params[0].is_cuda:
@@ -157,6 +162,44 @@ def weighted_delta_accum(delta: Sequence[torch.Tensor],
             diff = cw.float() - gw.float().unsqueeze(0)
             shape = [-1] + [1] * (cw.dim() - 1)
             dl.add_((diff * weights.view(shape)).sum(dim=0))
+
+
+def client_delta_sqnorm(client_params: Sequence[torch.Tensor],
+                        global_params: Sequence[torch.Tensor]) -> torch.Tensor:
+    """sq[c] = sum_i ||client_params[i][c] - global_params[i]||^2 as fp32
+    [C]: each client's squared update norm over all parameters.  The
+    difference is taken per element in fp32.  GPU: one deterministic
+    reduction per parameter (csrc/clip.hip), no host read."""
+    C = client_params[0].shape[0]
+    dev = client_params[0].device
+    sq = torch.zeros(C, dtype=torch.float32, device=dev)
+    if client_params[0].is_cuda:
+        ops = load_hip_ops(required=True)
+        for cw, gw in zip(client_params, global_params):
+            ops.client_delta_sqnorm(sq, cw.detach().reshape(-1),
+                                    gw.detach().reshape(-1), C)
+        return sq
+    with torch.no_grad():
+        for cw, gw in zip(client_params, global_params):
+            diff = cw.float() - gw.float().unsqueeze(0)
+            sq.add_((diff * diff).reshape(C, -1).sum(dim=1))
+    return sq
+
+
+def clip_weights(sq: torch.Tensor, weights: torch.Tensor, clip_norm: float):
+    """Aggregation weights of norm-clipped updates.  With s_c = S /
+    sqrt(sq[c]) where sq[c] > S^2 and 1 elsewhere (S = clip_norm in fp32),
+    returns (w_eff, wsum_eff): w_eff[c] = weights[c] * s_c as fp32 [C] and
+    their sum as fp32 [1], both on sq's device."""
+    if sq.is_cuda:
+        ops = load_hip_ops(required=True)
+        return ops.clip_weights(sq, weights.float().contiguous(),
+                                float(clip_norm))
+    with torch.no_grad():
+        S = torch.tensor(float(clip_norm), dtype=torch.float32)
+        s = torch.where(sq > S * S, S / sq.sqrt(), torch.ones_like(sq))
+        w_eff = weights.float() * s
+        return w_eff, w_eff.sum().reshape(1)
 
 
 def apply_aggregate(global_params: Sequence[torch.Tensor],
@@ -209,10 +252,18 @@ def weighted_delta_accum_flat(delta: torch.Tensor, buf: torch.Tensor,
                               global_flat: torch.Tensor,
                               weights: torch.Tensor, clients: int,
                               offsets: Optional[torch.Tensor] = None,
-                              wsum: Optional[float] = None) -> None:
-    """delta[j] += sum_c weights[c] * (buf[c,j] - global_flat[j]) per block."""
+                              wsum: Union[float, torch.Tensor, None] = None
+                              ) -> None:
+    """delta[j] += sum_c weights[c] * (buf[c,j] - global_flat[j]) per block.
+    wsum: host float or one-element fp32 device tensor (see
+    weighted_delta_accum)."""
     if buf.is_cuda:
         ops = load_hip_ops(required=True)
+        if isinstance(wsum, torch.Tensor):
+            ops.weighted_delta_accum_flat_dw(delta, buf, global_flat,
+                                             weights.float(), offsets,
+                                             int(clients), wsum)
+            return
         if wsum is None:
             wsum = float(weights.sum())
         ops.weighted_delta_accum_flat(delta, buf, global_flat,

@@ -16,7 +16,8 @@ use, writes logical_target/device_target rows, and launches
 Operator knobs come from the train operator's `operator_params` JSON
 (the operator-facing API of taskMgr/base/base_operator.py:12-53):
 model, lr, local_steps, batch_size, prox_mu, cohort_size, num_classes,
-dirichlet_alpha, dtype, chunk_clients, vocab_size, seq_len.
+dirichlet_alpha, dtype, chunk_clients, vocab_size, seq_len, clip_norm,
+noise_multiplier, update_norm_stats.
 """
 
 from __future__ import annotations
@@ -126,6 +127,9 @@ def engine_job_from_task(task: TaskConfig, allocations: List[DataAllocation],
         batch_size=params.get("batch_size", 8),
         lr=params.get("lr", 0.05),
         prox_mu=params.get("prox_mu", 0.0),
+        clip_norm=float(params.get("clip_norm", 0.0)),
+        noise_multiplier=float(params.get("noise_multiplier", 0.0)),
+        update_norm_stats=bool(params.get("update_norm_stats", False)),
         dtype=params.get("dtype", "float32" if device == "cpu" else "bfloat16"),
         device=device,
         chunk_clients=params.get("chunk_clients", 0),
