@@ -91,8 +91,11 @@ def replicate_params(cast_params: Params, clients: int) -> Params:
     out: Params = {}
     for k, v in cast_params.items():
         vd = v.detach()
+        # data_ptr: v is a view into the flat cast at any element offset
+        # and the kernel loads 16 bytes at a time
         if (ops is not None and vd.numel() % 8 == 0
-                and vd.dtype in (torch.bfloat16, torch.float32)):
+                and vd.dtype in (torch.bfloat16, torch.float32)
+                and vd.data_ptr() % 16 == 0):
             # broadcast kernel (replicate.hip): torch's expand().clone()
             # runs the stride-0 source through an unvectorised copy
             # (~0.39 TB/s measured; ~65 ms/round on the flagship)

@@ -17,6 +17,7 @@
 // clipped aggregation needs no host round trip per chunk).
 
 #include "common.h"
+#include "delta_route.h"
 #include "ols_ops.h"
 
 #define MAX_LDS_W 4096
@@ -151,13 +152,23 @@ __global__ __launch_bounds__(OLS_THREADS) void k_delta_accum_cpar_s(
   atomicAdd(&delta[j], acc);
 }
 
+extern "C" const char* ols_delta_accum_route(int nblocks, int64_t n,
+                                             int64_t clients, int dtype,
+                                             int master_16b, int buf_16b) {
+  return delta_route_name(delta_accum_route(nblocks, n, clients, dtype,
+                                            master_16b != 0, buf_16b != 0));
+}
+
 extern "C" void ols_weighted_delta_accum_flat(
     float* delta, const void* buf, const void* master, const float* weights,
     const int64_t* offs, int nblocks, int64_t clients, int64_t pglobal,
     float wsum, const float* wsum_dev, int dtype, hipStream_t stream) {
   dim3 block(OLS_THREADS);
-  if (nblocks == 1 && pglobal % 8 != 0 && dtype == 1 &&
-      pglobal < 131072 && clients >= 64) {
+  const DeltaRoute route = delta_accum_route(
+      nblocks, pglobal, clients, dtype,
+      reinterpret_cast<uintptr_t>(master) % 16 == 0,
+      reinterpret_cast<uintptr_t>(buf) % 16 == 0);
+  if (route == DELTA_CPAR_S) {
     const int ctile = 64;
     dim3 grid((unsigned)((pglobal + OLS_THREADS - 1) / OLS_THREADS),
               (unsigned)((clients + ctile - 1) / ctile));
@@ -167,10 +178,7 @@ extern "C" void ols_weighted_delta_accum_flat(
                        pglobal, wsum, wsum_dev, ctile);
     return;
   }
-  if (nblocks == 1 && pglobal % 8 == 0 && dtype == 1 &&
-      pglobal / 8 < 16384 && clients >= 64) {
-    // small param: client-parallel tiles (fills the chip; the j-only
-    // kernel would be a serial latency chain on a handful of lanes)
+  if (route == DELTA_CPAR) {
     const int ctile = 64;
     dim3 grid((unsigned)((pglobal / 8 + OLS_THREADS - 1) / OLS_THREADS),
               (unsigned)((clients + ctile - 1) / ctile));
@@ -180,7 +188,7 @@ extern "C" void ols_weighted_delta_accum_flat(
                        pglobal, wsum, wsum_dev, ctile);
     return;
   }
-  if (nblocks == 1 && pglobal % 8 == 0 && dtype != 0) {
+  if (route == DELTA_V8) {
     dim3 grid(ols_grid(pglobal / 8, OLS_THREADS));
     if (dtype == 1)
       hipLaunchKernelGGL((k_delta_accum_v8<__hip_bfloat16>), grid, block, 0,

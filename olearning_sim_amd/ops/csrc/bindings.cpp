@@ -82,6 +82,21 @@ void weighted_delta_accum_flat_dw(at::Tensor delta, at::Tensor buf,
                    wsum.data_ptr<float>());
 }
 
+// The kernel one accumulate launch runs: "cpar_s", "cpar", "v8" or
+// "block_table".  dtype 0 fp32, 1 bf16, 2 fp16; the two flags say whether
+// master and buf start on a 16-byte boundary.  Same host function the
+// launcher switches on (delta_route.h), which reads the flags off the
+// pointers it is given.
+std::string delta_accum_route(int64_t nblocks, int64_t n, int64_t clients,
+                              int64_t dtype, bool master_aligned,
+                              bool buf_aligned) {
+  TORCH_CHECK(nblocks >= 1 && n >= 0 && clients >= 1 && dtype >= 0 &&
+                  dtype <= 2,
+              "delta_accum_route: nblocks >= 1, clients >= 1, dtype 0..2");
+  return ols_delta_accum_route((int)nblocks, n, clients, (int)dtype,
+                               master_aligned, buf_aligned);
+}
+
 // ---- per-client update clipping (clip.hip) ------------------------------
 
 // 16 / itemsize when every row of buf [clients, n] and master start on a
@@ -782,6 +797,10 @@ at::Tensor replicate(at::Tensor src, int64_t clients) {
   TORCH_CHECK(src.numel() % 8 == 0);
   TORCH_CHECK(src.scalar_type() == at::kBFloat16 ||
               src.scalar_type() == at::kFloat);
+  // k_replicate reads src as 16-byte packs; a view into a flat buffer
+  // can start anywhere (replicate_params clones those instead)
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(src.data_ptr()) % 16 == 0,
+              "replicate: src must start on a 16-byte boundary");
   auto sizes = src.sizes().vec();
   sizes.insert(sizes.begin(), clients);
   auto dst = at::empty(sizes, src.options());
@@ -867,6 +886,8 @@ TORCH_LIBRARY(olsim_hip, m) {
   m.def("weighted_delta_accum_flat_dw(Tensor(a!) delta, Tensor buf, "
         "Tensor global_flat, Tensor weights, Tensor offsets, int clients, "
         "Tensor wsum) -> ()");
+  m.def("delta_accum_route(int nblocks, int n, int clients, int dtype, "
+        "bool master_aligned, bool buf_aligned) -> str", &delta_accum_route);
   m.def("client_delta_sqnorm(Tensor(a!) sq, Tensor buf, Tensor master, "
         "int clients) -> ()");
   m.def("sqnorm_tiles(int n, int clients, int vec) -> int", &sqnorm_tiles);

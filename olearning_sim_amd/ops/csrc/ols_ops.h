@@ -22,6 +22,13 @@ extern "C" void ols_weighted_delta_accum_flat(
     const int64_t* offs, int nblocks, int64_t clients, int64_t pglobal,
     float wsum, const float* wsum_dev, int dtype, hipStream_t stream);
 
+// "cpar_s", "cpar", "v8" or "block_table": the kernel that launch runs for
+// nblocks blocks of n master elements in all (delta_route.h), given
+// whether master and buf start on 16-byte boundaries
+extern "C" const char* ols_delta_accum_route(int nblocks, int64_t n,
+                                             int64_t clients, int dtype,
+                                             int master_16b, int buf_16b);
+
 // clip.hip: per-client squared update norm and clipped aggregation weights
 extern "C" int ols_sqnorm_tiles(int64_t n, int64_t clients, int vec);
 extern "C" void ols_client_delta_sqnorm(float* sq, float* part,

@@ -458,3 +458,148 @@ def test_model_gradient_check_accepts_standin_rejects_1pct(name, monkeypatch):
     for mutant in ("dx", "dw", "db"):
         with pytest.raises(AssertionError):
             run(mutant)
+
+
+# -- the local trainer's chunk ----------------------------------------------
+
+def _trainer_mutants(monkeypatch, model, C):
+    """name -> context-free patcher of one of LocalTrainer's collaborators
+    (ops.fused, the model); LocalTrainer itself is left alone."""
+    from olearning_sim_amd.ops import fused
+    real_sgd, real_accum = fused.fused_sgd_update, fused.weighted_delta_accum
+    real_loss = model.loss
+
+    def sgd(lr_scale=1.0, no_prox=False, skip_last=False):
+        def patched(params, grads, lr, mu=0.0, global_params=None,
+                    keep_wt=False):
+            if skip_last and not keep_wt:       # keep_wt is False only there
+                return
+            real_sgd(params, grads, lr * lr_scale, 0.0 if no_prox else mu,
+                     global_params, keep_wt)
+        return lambda: monkeypatch.setattr(fused, "fused_sgd_update", patched)
+
+    def accum(client, value=None, scale=1.0):
+        def patched(delta, client_params, global_params, weights, wsum=None):
+            w = weights.clone()
+            w[client] = (w[client] if value is None else value) * scale
+            real_accum(delta, client_params, global_params, w, wsum)
+        return lambda: monkeypatch.setattr(fused, "weighted_delta_accum",
+                                           patched)
+
+    return {
+        # gradient of the chunk mean: the trainer's "* C" has nothing to undo
+        "chunk_mean": lambda: monkeypatch.setattr(
+            model, "loss", lambda p, x, y: real_loss(p, x, y) / C,
+            raising=False),
+        "no_prox": sgd(no_prox=True),
+        "skip_last_step": sgd(skip_last=True),
+        "clip_ignored": lambda: monkeypatch.setattr(
+            fused, "clip_weights",
+            lambda sq, w, S: (w.float(), w.float().sum().reshape(1))),
+        "zero_weight_counted": accum(1, value=1.0),
+        "lr_1pct": sgd(lr_scale=1.01),
+        "weight_1pct": accum(0, scale=1.01),
+    }
+
+
+@pytest.mark.parametrize("name", ["mlp", "lstm", "bert"])
+def test_trainer_check_accepts_cpu_trainer_rejects_mutants(name, monkeypatch):
+    case = kb.trainer_case(name)                 # before anything is patched
+    assert 0 < case["e_cpu32"] and case["tol"] <= 0.05
+    for clip in kb.TRAINER_CLIPS:
+        kb.assert_trainer_bounded(name, *kb.trainer_run(name, clip),
+                                  clip=clip)
+        kb.assert_trainer_bounded(
+            name, *kb.trainer_run(name, clip, chunks=((0, 1), (2,))),
+            clip=clip)
+
+    def rejected(mutant, clip):
+        with monkeypatch.context() as mp:
+            _trainer_mutants(mp, case["model"], case["C"])[mutant]()
+            delta, sq = kb.trainer_run(name, clip)
+        with pytest.raises(AssertionError):
+            kb.assert_trainer_bounded(name, delta, sq, clip=clip)
+
+    for mutant in ("chunk_mean", "no_prox", "skip_last_step",
+                   "zero_weight_counted"):
+        for clip in kb.TRAINER_CLIPS:
+            rejected(mutant, clip)
+    for clip in ("all", "one"):
+        rejected("clip_ignored", clip)
+        # the clip factor folded into the weights but not into their sum.
+        # The CPU accumulate subtracts the master per client and never
+        # reads wsum, so the mutant is formed from the honest result:
+        # sum_c w_c s_c p_c - (sum_c w_c) p_global
+        #   = delta - (sum_c w_c - sum_c w_c s_c) p_global
+        ref = case["ref"][clip]
+        delta, sq = kb.trainer_run(name, clip)
+        lost = sum(kb.TRAINER_WEIGHTS) - float(ref["w_eff"].sum())
+        assert lost > 0
+        bad = {k: d.double() - lost * case["g64"][k] for k, d in delta.items()}
+        with pytest.raises(AssertionError):
+            kb.assert_trainer_bounded(name, bad, sq, clip=clip)
+    if name == "mlp":
+        # 1 % moves the result by about 5e-3 of max|delta|: far outside
+        # MLP's tol, inside the LSTM's and BERT's
+        for mutant in ("lr_1pct", "weight_1pct"):
+            for clip in kb.TRAINER_CLIPS:
+                rejected(mutant, clip)
+
+
+def test_trainer_reference_and_fixed_data_are_what_they_say():
+    """trainer_math on a model whose gradient is known in closed form, and
+    FixedData's indexing."""
+
+    class Quad:
+        sequence_model = False
+
+        def forward(self, params, x):          # logits = x * w, K = 2
+            return x * params["w"].unsqueeze(1)
+
+    # one row per client, label 0: loss = log(1 + exp((w1 - w0) x)) at
+    # x = (1, 1); d/dw0 = -sigmoid(w1 - w0), d/dw1 = +sigmoid(w1 - w0)
+    gp = {"w": torch.tensor([0.25, -0.5])}
+    x = torch.ones(2, 1, 2)
+    y = torch.zeros(2, 1, dtype=torch.int64)
+    delta, sq, w_eff = kb.trainer_math(Quad(), gp, [(x, y)], [2.0, 1.0],
+                                       lr=0.5, mu=0.5, steps=1, clip_norm=0.0)
+    sg = float(torch.sigmoid(torch.tensor(-0.75, dtype=torch.float64)))
+    step = 0.5 * sg                              # prox term is 0 at step 1
+    want = torch.tensor([step, -step], dtype=torch.float64) * 3.0
+    assert torch.allclose(delta["w"], want, rtol=1e-12, atol=0)
+    assert torch.allclose(sq, torch.full((2,), 2 * step * step,
+                                         dtype=torch.float64), rtol=1e-12)
+    S = 0.5 * (2 * step * step) ** 0.5
+    delta, sq, w_eff = kb.trainer_math(Quad(), gp, [(x, y)], [2.0, 1.0],
+                                       lr=0.5, mu=0.5, steps=1, clip_norm=S)
+    assert torch.allclose(w_eff, torch.tensor([1.0, 0.5], dtype=torch.float64),
+                          rtol=1e-6)
+    assert torch.allclose(delta["w"], want / 2, rtol=1e-6, atol=0)
+
+    data = kb.FixedData([(torch.arange(12.0).view(3, 2, 2),
+                          torch.arange(6).view(3, 2))])
+    xs, ys = data.batch(torch.tensor([2, 0]), 0, 0, 2, torch.bfloat16)
+    assert xs.dtype == torch.bfloat16 and xs[:, 0, 0].tolist() == [8.0, 0.0]
+    assert ys.tolist() == [[4, 5], [0, 1]]
+
+
+# -- operand layout of the bundled models -----------------------------------
+
+@pytest.mark.parametrize("name", ["resnet18", "bert", "lstm", "mlp"])
+def test_default_layouts_keep_vector_eligible_parameters_aligned(name):
+    """replicate and the vector accumulate kernels read a parameter with
+    numel % 8 == 0 as 16-byte packs, and refuse (clone, scalar kernel) a
+    view that does not start on a 16-byte boundary.  In the default
+    layouts every such parameter starts at a multiple of 8 elements of
+    the flat master - 16 bytes in bf16 and fp16, 32 in fp32 - so the
+    alignment guards leave these models on the kernels they ran before."""
+    from olearning_sim_amd.models import build_model
+    params = build_model(name).init_global(device="meta")
+    off, eligible = 0, 0
+    for key, v in params.items():
+        n = v.numel()
+        if n % 8 == 0:
+            eligible += 1
+            assert off % 8 == 0, f"{name}: {key} starts at element {off}"
+        off += n
+    assert eligible > 0
