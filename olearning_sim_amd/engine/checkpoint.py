@@ -73,3 +73,45 @@ def load_checkpoint(directory: str, task_id: str, current_round: int,
     if not os.path.exists(path):
         return None
     return load_file(path, device=device)
+
+
+# -- server optimiser sidecar ------------------------------------------------
+#
+# The round artifact stays model-only (users load it); the optimiser's m, v
+# and step count of the same round go into a file next to it.  The suffix
+# follows the artifact's whole name, so latest_round's anchored pattern
+# never takes a sidecar for an artifact.
+
+SERVER_OPT_SUFFIX = ".server_opt.safetensors"
+
+
+def server_opt_name(task_id: str, current_round: int,
+                    model_update_style: str = "") -> str:
+    return checkpoint_name(task_id, current_round,
+                           model_update_style) + SERVER_OPT_SUFFIX
+
+
+def save_server_opt(directory: str, task_id: str, current_round: int,
+                    state: Dict[str, torch.Tensor],
+                    model_update_style: str = "") -> str:
+    from safetensors.torch import save_file
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, server_opt_name(
+        task_id, current_round, model_update_style))
+    save_file({k: v.detach().cpu().contiguous() for k, v in state.items()}, path)
+    return path
+
+
+def load_server_opt(directory: str, task_id: str, current_round: int,
+                    model_update_style: str = "",
+                    device: str = "cpu") -> Dict[str, torch.Tensor]:
+    """The sidecar of round current_round.  A missing file is an error:
+    resuming with zeroed optimiser state would silently change results."""
+    from safetensors.torch import load_file
+    path = os.path.join(directory, server_opt_name(
+        task_id, current_round, model_update_style))
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"server optimiser state {path} is missing: cannot resume round "
+            f"{current_round + 1} with server_optimizer on")
+    return load_file(path, device=device)

@@ -37,6 +37,19 @@ class EngineJob:
     noise_multiplier: float = 0.0
     update_norm_stats: bool = False
 
+    # server optimiser: "" applies the aggregate as it is (master +=
+    # delta / total_weight); "momentum" (FedAvgM), "adagrad", "adam" and
+    # "yogi" (FedOpt, no bias correction) treat g = delta / total_weight
+    # as a pseudo-gradient: m = beta1*m + (1-beta1)*g (momentum: + g), v
+    # per kind from v0 = tau^2, master += server_lr * m / (sqrt(v) + tau)
+    # (momentum: server_lr * m).  With noise on, sigma * z enters g before
+    # the step and nothing is added to the master afterwards.
+    server_optimizer: str = ""
+    server_lr: float = 1.0
+    server_beta1: float = 0.9
+    server_beta2: float = 0.99
+    server_tau: float = 1e-3
+
     # execution
     dtype: str = "float32"          # compute dtype of client replicas
     device: str = "cpu"

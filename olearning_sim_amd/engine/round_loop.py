@@ -25,7 +25,9 @@ import torch
 from ..models import build_model
 from ..ops import fused
 from ..parallel import dist as pdist
-from .checkpoint import save_checkpoint, load_checkpoint, latest_round
+from . import server_opt
+from .checkpoint import (save_checkpoint, load_checkpoint, latest_round,
+                         save_server_opt, load_server_opt)
 from .client_manager import FlatParams
 from .data import SyntheticFederatedData
 from .job import EngineJob
@@ -73,6 +75,15 @@ class LogicalEngine:
         if self.ctx.enabled:
             # all ranks seed identically, but broadcast pins exact equality
             pdist.broadcast_flat(self.master.flat)
+        # server optimiser state (m, v): allocated here, so that it is
+        # already held when _chunk_size probes the free memory; the
+        # constructor raises ValueError on a setting no rule is defined for
+        self.server_opt: Optional[server_opt.ServerOptimizer] = None
+        if job.server_optimizer:
+            self.server_opt = server_opt.ServerOptimizer(
+                job.server_optimizer, self.master.numel(), self.device,
+                lr=job.server_lr, beta1=job.server_beta1,
+                beta2=job.server_beta2, tau=job.server_tau)
 
         self.data = SyntheticFederatedData(
             clients=job.clients, num_classes=job.num_classes,
@@ -144,6 +155,12 @@ class LogicalEngine:
                 if sd is not None:
                     self.master.load_state_dict(sd)
                     self.start_round = r + 1
+                    if self.server_opt is not None:
+                        # every rank loads; a missing sidecar raises
+                        self.server_opt.load_state_dict(load_server_opt(
+                            job.checkpoint_dir, job.task_id, r,
+                            job.model_update_style,
+                            device=str(self.device)))
 
     # ------------------------------------------------------------------
     def _chunk_size(self, cohort: int) -> int:
@@ -216,25 +233,49 @@ class LogicalEngine:
         if work is not None:
             work.wait()
         if total_weight > 0:
+            self._apply_update(delta, total_weight, round_idx)
+
+    def _apply_update(self, delta: torch.Tensor, total_weight: float,
+                      round_idx: int) -> None:
+        """Fold a round's reduced delta (total_weight > 0) into the master:
+        the one place both aggregation paths end in.  Without a server
+        optimiser, master += delta / total_weight and then the noise.  With
+        one, delta / total_weight + sigma * z is the optimiser's
+        pseudo-gradient: the noise goes in before the step, which is then
+        post-processing of the Gaussian mechanism, and nothing is added to
+        the master afterwards."""
+        if self.server_opt is None:
             fused.apply_aggregate([self.master.flat], [delta], total_weight)
             self._add_noise(round_idx, total_weight)
+            return
+        sigma, noise = self._noise(round_idx, total_weight)
+        self.server_opt.step(self.master.flat, delta, total_weight,
+                             noise=noise, sigma=sigma)
 
-    def _add_noise(self, round_idx: int, total_weight: float) -> None:
-        """master += N(0, sigma^2) per coordinate, sigma = noise_multiplier
-        * clip_norm / total_weight: the Gaussian mechanism on the clipped
-        mean.  The generator is seeded from (job.seed, round_idx) and not
-        from the rank, so every rank adds the same tensor and the masters
-        stay equal, and a resumed run draws the noise it would have drawn."""
+    def _noise(self, round_idx: int, total_weight: float):
+        """(sigma, z): the round's noise scale noise_multiplier * clip_norm
+        / total_weight and standard normal tensor, or (0.0, None) with
+        noise off.  The generator is seeded from (job.seed, round_idx) and
+        not from the rank, so every rank draws the same tensor and the
+        masters stay equal, and a resumed run draws the noise it would
+        have drawn."""
         job = self.job
         if job.noise_multiplier <= 0 or total_weight <= 0:
-            return
+            return 0.0, None
         sigma = job.noise_multiplier * job.clip_norm / total_weight
         gen = torch.Generator(device=self.device)
         gen.manual_seed((job.seed * 1_000_003 + round_idx * 7919 + 0x5EED)
                         % (2 ** 63))
         noise = torch.randn(self.master.flat.shape, generator=gen,
                             device=self.device, dtype=self.master.flat.dtype)
-        self.master.flat.add_(noise, alpha=sigma)
+        return sigma, noise
+
+    def _add_noise(self, round_idx: int, total_weight: float) -> None:
+        """master += N(0, sigma^2) per coordinate: the Gaussian mechanism
+        on the clipped mean (_noise)."""
+        sigma, noise = self._noise(round_idx, total_weight)
+        if noise is not None:
+            self.master.flat.add_(noise, alpha=sigma)
 
     def _update_norm_counts(self, chunks) -> List[float]:
         """[clipped, sum of norms, clients] over this rank's clients of
@@ -360,9 +401,7 @@ class LogicalEngine:
             total_weight = local_weight
             success, failed = success_local, failed_local
             if total_weight > 0:
-                fused.apply_aggregate([self.master.flat], [self._delta],
-                                      total_weight)
-                self._add_noise(round_idx, total_weight)
+                self._apply_update(self._delta, total_weight, round_idx)
 
         self.success_total += success
         self.failed_total += failed
@@ -468,9 +507,7 @@ class LogicalEngine:
             elif kind == "checkpoint":
                 self._finish_aggregate()
                 if self.ctx.rank == 0 and job.checkpoint_dir:
-                    record["checkpoint"] = save_checkpoint(
-                        job.checkpoint_dir, job.task_id, round_idx,
-                        self.master.state_dict(), job.model_update_style)
+                    record["checkpoint"] = self._save_round(round_idx)
             self.last_operator = name
         if job.eval_every > 0 and (round_idx + 1) % job.eval_every == 0                 and "eval_acc" not in record:
             record.update(self.evaluate_global(round_idx))
@@ -487,10 +524,21 @@ class LogicalEngine:
         if job.save_every_round and job.checkpoint_dir                 and "checkpoint" not in record:
             self._finish_aggregate()
             if self.ctx.rank == 0:
-                record["checkpoint"] = save_checkpoint(
-                    job.checkpoint_dir, job.task_id, round_idx,
-                    self.master.state_dict(), job.model_update_style)
+                record["checkpoint"] = self._save_round(round_idx)
         return record
+
+    def _save_round(self, round_idx: int) -> str:
+        """Write round round_idx's model artifact and, with a server
+        optimiser on, its state next to it; returns the artifact's path."""
+        job = self.job
+        path = save_checkpoint(job.checkpoint_dir, job.task_id, round_idx,
+                               self.master.state_dict(),
+                               job.model_update_style)
+        if self.server_opt is not None:
+            save_server_opt(job.checkpoint_dir, job.task_id, round_idx,
+                            self.server_opt.state_dict(),
+                            job.model_update_style)
+        return path
 
     # ------------------------------------------------------------------
     def run(self) -> Dict[str, Any]:

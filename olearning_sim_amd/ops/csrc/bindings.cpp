@@ -170,6 +170,61 @@ std::tuple<at::Tensor, at::Tensor> clip_weights(at::Tensor sq,
   return {w_eff, wsum_eff};
 }
 
+// ---- server optimiser step (server_opt.hip) ------------------------------
+// kind 0 momentum, 1 adagrad, 2 adam, 3 yogi.  x (master), m and v are
+// updated in place; momentum has no v and takes an empty one.  z is the
+// round's noise or None: g = d / total_weight + sigma * z.
+
+void server_opt_step(int64_t kind, at::Tensor x, at::Tensor d, at::Tensor m,
+                     at::Tensor v, const c10::optional<at::Tensor>& z,
+                     double total_weight, double sigma, double lr,
+                     double beta1, double beta2, double tau) {
+  TORCH_CHECK(kind >= 0 && kind <= 3, "server_opt_step: kind ", kind,
+              " outside 0..3 (momentum, adagrad, adam, yogi)");
+  TORCH_CHECK(total_weight > 0.0,
+              "server_opt_step: total_weight must be positive, got ",
+              total_weight);
+  TORCH_CHECK(x.is_cuda(), "server_opt_step: x must be on the GPU");
+  const bool has_z = z.has_value() && z->defined();
+  auto check = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == x.device() &&
+                    t.scalar_type() == at::kFloat && t.is_contiguous(),
+                "server_opt_step: ", name,
+                " must be contiguous fp32 on the GPU of x");
+  };
+  check(x, "x");
+  check(d, "d");
+  check(m, "m");
+  check(v, "v");
+  if (has_z) check(*z, "z");
+  const int64_t n = x.numel();
+  TORCH_CHECK(d.numel() == n && m.numel() == n &&
+                  (!has_z || z->numel() == n),
+              "server_opt_step: x, d, m and z must have one numel, got ", n,
+              ", ", d.numel(), ", ", m.numel(), ", ",
+              has_z ? z->numel() : n);
+  TORCH_CHECK(v.numel() == n || (kind == 0 && v.numel() == 0),
+              "server_opt_step: v has ", v.numel(), " elements, expected ",
+              n, kind == 0 ? " or none" : "");
+  if (n == 0) return;
+  ols_server_opt_step((int)kind, x.data_ptr<float>(), d.data_ptr<float>(),
+                      m.data_ptr<float>(),
+                      kind == 0 ? nullptr : v.data_ptr<float>(),
+                      has_z ? z->data_ptr<float>() : nullptr, n,
+                      (float)(1.0 / total_weight), (float)sigma, (float)lr,
+                      (float)beta1, (float)beta2, (float)tau,
+                      at::cuda::getCurrentCUDAStream().stream());
+}
+
+// "v4" or "scalar": the kernel a step over n elements runs, given whether
+// every operand starts on a 16-byte boundary.  Same host function the
+// launcher switches on (server_opt_route.h), which reads the flag off the
+// pointers it is given.
+std::string server_opt_route(int64_t n, bool aligned) {
+  TORCH_CHECK(n >= 0, "server_opt_route: n >= 0");
+  return ols_server_opt_route(n, aligned);
+}
+
 std::tuple<at::Tensor, at::Tensor> cross_entropy_fwd_bwd(at::Tensor logits,
                                                          at::Tensor labels) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous());
@@ -893,6 +948,10 @@ TORCH_LIBRARY(olsim_hip, m) {
   m.def("sqnorm_tiles(int n, int clients, int vec) -> int", &sqnorm_tiles);
   m.def("clip_weights(Tensor sq, Tensor weights, float clip_norm) -> "
         "(Tensor, Tensor)");
+  m.def("server_opt_step(int kind, Tensor(a!) x, Tensor d, Tensor(b!) m, "
+        "Tensor(c!) v, Tensor? z, float total_weight, float sigma, float lr, "
+        "float beta1, float beta2, float tau) -> ()");
+  m.def("server_opt_route(int n, bool aligned) -> str", &server_opt_route);
   m.def("cross_entropy_fwd_bwd(Tensor logits, Tensor labels) -> (Tensor, Tensor)");
   m.def("groupnorm_fwd(Tensor x, Tensor res, Tensor gamma, Tensor beta, "
         "int clients, int groups, float eps, bool relu) -> (Tensor, Tensor, Tensor)");
@@ -948,6 +1007,7 @@ TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("weighted_delta_accum_flat_dw", &weighted_delta_accum_flat_dw);
   m.impl("client_delta_sqnorm", &client_delta_sqnorm);
   m.impl("clip_weights", &clip_weights);
+  m.impl("server_opt_step", &server_opt_step);
   m.impl("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.impl("groupnorm_fwd", &groupnorm_fwd);
   m.impl("groupnorm_bwd", &groupnorm_bwd);

@@ -40,6 +40,19 @@ extern "C" void ols_clip_weights(const float* sq, const float* weights,
                                  int64_t clients, float clip,
                                  hipStream_t stream);
 
+// server_opt.hip: one server optimiser step over the flat fp32 master.
+// kind 0 momentum, 1 adagrad, 2 adam, 3 yogi (server_opt_route.h);
+// x, m, v in place, v unused (may be null) for momentum, z null for no
+// noise: g = d*inv_w + sigma*z
+extern "C" void ols_server_opt_step(int kind, float* x, const float* d,
+                                    float* m, float* v, const float* z,
+                                    int64_t n, float inv_w, float sigma,
+                                    float lr, float b1, float b2, float tau,
+                                    hipStream_t stream);
+// "v4" or "scalar": the kernel that step runs for n elements, given
+// whether every operand starts on a 16-byte boundary
+extern "C" const char* ols_server_opt_route(int64_t n, int aligned);
+
 extern "C" void ols_cross_entropy_fwd_bwd(
     const void* logits, const int64_t* labels, float* loss, void* dlogits,
     int64_t nrows, int64_t K, float inv_n, int dtype, hipStream_t stream);

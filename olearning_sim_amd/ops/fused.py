@@ -9,6 +9,9 @@ aggregation tail of every local-train step:
                          (mu=0 -> FedAvg local SGD; mu>0 -> FedProx)
 - weighted_delta_accum:  delta += sum_c alpha_c * (w_c - w_global)
 - apply_aggregate:       w_global += delta / total_weight  (fp32 master)
+- server_opt_step:       FedAvgM / FedAdagrad / FedAdam / FedYogi step on
+                         the fp32 master with g = delta / total_weight
+                         [+ sigma * noise], m and v in place, one launch
 - cross_entropy_fwd_bwd: fused softmax CE loss + dlogits in one pass
 
 On ROCm these run as hand-written gfx950 kernels (csrc/*.hip, bf16x8 per
@@ -212,6 +215,76 @@ def apply_aggregate(global_params: Sequence[torch.Tensor],
         inv = 1.0 / float(total_weight)
         torch._foreach_add_([g for g in global_params],
                             [d for d in delta], alpha=inv)
+
+
+# -- server optimiser step --------------------------------------------------
+
+SERVER_OPT_KINDS = ("momentum", "adagrad", "adam", "yogi")
+
+
+def server_opt_step_eager(kind: str, master: torch.Tensor,
+                          delta: torch.Tensor, m: torch.Tensor,
+                          v: Optional[torch.Tensor], total_weight: float,
+                          lr: float, beta1: float, beta2: float, tau: float,
+                          noise: Optional[torch.Tensor] = None,
+                          sigma: float = 0.0) -> None:
+    """The rule of server_opt_step composed from torch ops on whatever
+    device the tensors are on: the CPU path, and what the fused kernel is
+    timed against (tools/serveroptbench.py)."""
+    with torch.no_grad():
+        g = delta * (1.0 / float(total_weight))
+        if noise is not None:
+            g.add_(noise, alpha=float(sigma))
+        if kind == "momentum":
+            m.mul_(beta1).add_(g)
+            master.add_(m, alpha=lr)
+            return
+        m.mul_(beta1).add_(g, alpha=1.0 - beta1)
+        g2 = g * g
+        if kind == "adagrad":
+            v.add_(g2)
+        elif kind == "adam":
+            v.mul_(beta2).add_(g2, alpha=1.0 - beta2)
+        else:
+            v.sub_(g2 * torch.sign(v - g2), alpha=1.0 - beta2)
+        master.addcdiv_(m, v.sqrt().add_(tau), value=lr)
+
+
+def server_opt_step(kind: str, master: torch.Tensor, delta: torch.Tensor,
+                    m: torch.Tensor, v: Optional[torch.Tensor],
+                    total_weight: float, lr: float, beta1: float,
+                    beta2: float, tau: float,
+                    noise: Optional[torch.Tensor] = None,
+                    sigma: float = 0.0) -> None:
+    """One server optimiser step on the flat fp32 master, in place.
+
+    g = delta / total_weight + sigma * noise (noise None: no second term)
+
+    - "momentum": m = beta1*m + g;              master += lr*m
+    - "adagrad":  m = beta1*m + (1-beta1)*g;    v = v + g^2
+    - "adam":     same m;        v = beta2*v + (1-beta2)*g^2
+    - "yogi":     same m;        v = v - (1-beta2)*g^2*sign(v - g^2)
+    - the three adaptive kinds: master += lr*m / (sqrt(v) + tau)
+
+    No bias correction.  master, m and v (None or empty for "momentum")
+    are updated; delta and noise are only read.  total_weight == 0 takes
+    no step.  GPU: one launch (csrc/server_opt.hip)."""
+    if kind not in SERVER_OPT_KINDS:
+        raise ValueError(f"server optimiser {kind!r} not one of "
+                         f"{SERVER_OPT_KINDS}")
+    if total_weight == 0:
+        return
+    if master.is_cuda:
+        ops = load_hip_ops(required=True)
+        if v is None:
+            v = torch.empty(0, dtype=master.dtype, device=master.device)
+        ops.server_opt_step(SERVER_OPT_KINDS.index(kind), master, delta, m,
+                            v, noise, float(total_weight), float(sigma),
+                            float(lr), float(beta1), float(beta2),
+                            float(tau))
+        return
+    server_opt_step_eager(kind, master, delta, m, v, total_weight, lr, beta1,
+                          beta2, tau, noise, sigma)
 
 
 # -- flat (single-buffer) forms used by the engine hot path ----------------

@@ -17,7 +17,8 @@ Operator knobs come from the train operator's `operator_params` JSON
 (the operator-facing API of taskMgr/base/base_operator.py:12-53):
 model, lr, local_steps, batch_size, prox_mu, cohort_size, num_classes,
 dirichlet_alpha, dtype, chunk_clients, vocab_size, seq_len, clip_norm,
-noise_multiplier, update_norm_stats.
+noise_multiplier, update_norm_stats, server_optimizer, server_lr,
+server_beta1, server_beta2, server_tau.
 """
 
 from __future__ import annotations
@@ -130,6 +131,11 @@ def engine_job_from_task(task: TaskConfig, allocations: List[DataAllocation],
         clip_norm=float(params.get("clip_norm", 0.0)),
         noise_multiplier=float(params.get("noise_multiplier", 0.0)),
         update_norm_stats=bool(params.get("update_norm_stats", False)),
+        server_optimizer=str(params.get("server_optimizer", "")),
+        server_lr=float(params.get("server_lr", 1.0)),
+        server_beta1=float(params.get("server_beta1", 0.9)),
+        server_beta2=float(params.get("server_beta2", 0.99)),
+        server_tau=float(params.get("server_tau", 1e-3)),
         dtype=params.get("dtype", "float32" if device == "cpu" else "bfloat16"),
         device=device,
         chunk_clients=params.get("chunk_clients", 0),
