@@ -50,6 +50,16 @@ class EngineJob:
     server_beta2: float = 0.99
     server_tau: float = 1e-3
 
+    # uplink compression: each client's update is quantised to uplink_bits
+    # bits per weight (2, 4 or 8; 0 = off, exact fp32 updates) before it
+    # is aggregated: stochastic, unbiased, one fp32 scale per bucket of
+    # 512 elements of a parameter tensor (ops/fused.py).  The round record
+    # then carries uplink_bytes, uplink_bytes_per_client and uplink_ratio.
+    # With clip_norm > 0 the norm is taken on the raw update and the clip
+    # factor scales the quantised one, whose norm may exceed clip_norm;
+    # noise_multiplier > 0 is refused for that reason.
+    uplink_bits: int = 0
+
     # execution
     dtype: str = "float32"          # compute dtype of client replicas
     device: str = "cpu"

@@ -11,7 +11,8 @@ Hot path per local step:
   contiguous [C*P] replica buffer (ops/csrc/fused_update.hip).
 After the E steps, ONE weighted-delta reduction kernel folds
 (w_c - w_global) * alpha_c into the fp32 delta accumulator
-(ops/csrc/aggregate.hip).
+(ops/csrc/aggregate.hip); with uplink compression on, the kernel that
+quantises each update as it reads it (ops/csrc/uplink_quant.hip).
 """
 
 from __future__ import annotations
@@ -31,7 +32,8 @@ class LocalTrainer:
                  data: SyntheticFederatedData, lr: float, prox_mu: float,
                  local_steps: int, batch_size: int, dtype: torch.dtype,
                  report_loss: bool = True, clip_norm: float = 0.0,
-                 update_norm_stats: bool = False):
+                 update_norm_stats: bool = False, uplink_bits: int = 0,
+                 uplink_seed: int = 0, uplink_rank: int = 0):
         # report_loss=False avoids a device sync per chunk (bench path)
         self.report_loss = report_loss
         # clip_norm > 0: each client's update is scaled to norm <= clip_norm
@@ -39,6 +41,18 @@ class LocalTrainer:
         # returned even when nothing is clipped
         self.clip_norm = clip_norm
         self.update_norm_stats = update_norm_stats
+        # uplink_bits > 0: the updates are quantised to that many bits per
+        # weight as they are accumulated; (uplink_seed, uplink_rank) and
+        # the round key the draws (fused.uplink_key)
+        self.uplink_bits = uplink_bits
+        self.uplink_seed = uplink_seed
+        self.uplink_rank = uplink_rank
+        # where each parameter starts in the flat master
+        self._elem_offsets: Dict[str, int] = {}
+        off = 0
+        for k, n in master.numels.items():
+            self._elem_offsets[k] = off
+            off += n
         self.model = model
         self.master = master
         self.data = data
@@ -137,7 +151,18 @@ class LocalTrainer:
                     # their sum stays on the device for the accumulate
                     weights, wsum = fused.clip_weights(sq, weights,
                                                        self.clip_norm)
-            fused.weighted_delta_accum(
-                delta_views, final, glist, weights,
-                wsum=wsum if wsum is not None else float(weights.sum()))
+            if self.uplink_bits > 0:
+                # nothing is hoisted: no wsum.  The clip factor in the
+                # weights scales the quantised update (the quantiser is
+                # scale-equivariant).
+                fused.weighted_delta_accum_quant(
+                    delta_views, final, glist, weights, client_ids,
+                    self.uplink_bits,
+                    fused.uplink_key(self.uplink_seed, round_idx,
+                                     self.uplink_rank),
+                    [self._elem_offsets[k] for k in params])
+            else:
+                fused.weighted_delta_accum(
+                    delta_views, final, glist, weights,
+                    wsum=wsum if wsum is not None else float(weights.sum()))
         return out

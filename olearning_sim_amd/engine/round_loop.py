@@ -64,6 +64,18 @@ class LogicalEngine:
             # the noise scale is a multiple of the clip norm: without a
             # bound on the updates there is nothing to calibrate it to
             raise ValueError("noise_multiplier needs clip_norm > 0")
+        if job.uplink_bits not in (0,) + fused.UPLINK_BITS:
+            raise ValueError(f"uplink_bits {job.uplink_bits!r} not one of "
+                             f"{(0,) + fused.UPLINK_BITS}")
+        if job.uplink_bits > 0 and job.noise_multiplier > 0:
+            raise ValueError(
+                "uplink_bits > 0 does not compose with noise_multiplier > 0: "
+                "sigma is calibrated to the sensitivity clip_norm, which the "
+                "quantiser does not keep (a quantised update's norm may "
+                "exceed clip_norm)")
+        if job.uplink_bits > 0 and job.clients > 2 ** 32:
+            # client ids are hashed as 32-bit words
+            raise ValueError("uplink_bits > 0 needs clients <= 2^32")
         self.stop_requested = False
 
         self.model = build_model(job.model_name, **job.model_kwargs)
@@ -84,6 +96,14 @@ class LogicalEngine:
                 job.server_optimizer, self.master.numel(), self.device,
                 lr=job.server_lr, beta1=job.server_beta1,
                 beta2=job.server_beta2, tau=job.server_tau)
+        self.uplink_bytes_per_client = 0
+        if job.uplink_bits > 0:
+            if self.master.numel() > 2 ** 33:
+                # element pairs are hashed as 32-bit words
+                raise ValueError("uplink_bits > 0 needs a model of at most "
+                                 "2^33 parameters")
+            self.uplink_bytes_per_client = fused.uplink_bytes_per_client(
+                list(self.master.numels.values()), job.uplink_bits)
 
         self.data = SyntheticFederatedData(
             clients=job.clients, num_classes=job.num_classes,
@@ -96,7 +116,9 @@ class LogicalEngine:
             prox_mu=job.prox_mu, local_steps=job.local_steps,
             batch_size=job.batch_size, dtype=self.dtype,
             report_loss=result_sink is not None, clip_norm=job.clip_norm,
-            update_norm_stats=job.update_norm_stats)
+            update_norm_stats=job.update_norm_stats,
+            uplink_bits=job.uplink_bits, uplink_seed=job.seed,
+            uplink_rank=self.ctx.rank)
         if behavior is None and job.behavior_strategy:
             from ..deviceflow.sampler import BehaviorSampler
             behavior = BehaviorSampler(job.behavior_strategy,
@@ -433,6 +455,13 @@ class LogicalEngine:
                                           else None)
             record["clipped_frac"] = (n_clipped / n_live if n_live > 0
                                       else 0.0)
+        if job.uplink_bits > 0:
+            # every client that trained sent its message; a dropped one
+            # was lost in flight
+            per = self.uplink_bytes_per_client
+            record["uplink_bytes"] = success * per
+            record["uplink_bytes_per_client"] = per
+            record["uplink_ratio"] = per / (self.master.numel() * 4)
         return record
 
     def _op_script(self, round_idx: int, name: str) -> Dict[str, Any]:
@@ -521,6 +550,9 @@ class LogicalEngine:
             if "clipped_frac" in record:
                 self.perf.record(job.task_id, "clipped_frac",
                                  record["clipped_frac"], round_idx)
+            if "uplink_bytes" in record:
+                self.perf.record(job.task_id, "uplink_bytes",
+                                 record["uplink_bytes"], round_idx)
         if job.save_every_round and job.checkpoint_dir                 and "checkpoint" not in record:
             self._finish_aggregate()
             if self.ctx.rank == 0:

@@ -14,6 +14,9 @@ from .fused import (
     weighted_delta_accum,
     client_delta_sqnorm,
     clip_weights,
+    weighted_delta_accum_quant,
+    uplink_uniform,
+    uplink_bytes_per_client,
     apply_aggregate,
     cross_entropy_fwd_bwd,
 )
@@ -21,5 +24,6 @@ from .fused import (
 __all__ = [
     "hip_ops_available", "load_hip_ops", "fused_sgd_update",
     "weighted_delta_accum", "client_delta_sqnorm", "clip_weights",
+    "weighted_delta_accum_quant", "uplink_uniform", "uplink_bytes_per_client",
     "apply_aggregate", "cross_entropy_fwd_bwd",
 ]

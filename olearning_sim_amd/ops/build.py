@@ -20,7 +20,7 @@ def build(verbose: bool = True) -> str:
     os.makedirs(build_dir, exist_ok=True)
     sources = [os.path.join(csrc, f) for f in
                ("bindings.cpp", "fused_update.hip", "aggregate.hip",
-                "clip.hip", "server_opt.hip", "cross_entropy.hip", "groupnorm.hip", "client_conv.hip",
+                "clip.hip", "uplink_quant.hip", "server_opt.hip", "cross_entropy.hip", "groupnorm.hip", "client_conv.hip",
                 "client_conv2.hip", "conv3_wflip.hip", "client_conv5.hip", "pool2x2.hip", "transpose.hip", "layernorm.hip", "pad2d.hip",
                "replicate.hip")]
     from torch.utils.cpp_extension import load

@@ -170,6 +170,89 @@ std::tuple<at::Tensor, at::Tensor> clip_weights(at::Tensor sq,
   return {w_eff, wsum_eff};
 }
 
+// ---- uplink compression (uplink_quant.hip) ------------------------------
+
+// delta[q] += sum_c weights[c] * Q(buf[c,q] - master[q]) for one parameter
+// tensor: Q quantises each client's update to `bits` bits per weight,
+// stochastically and per bucket of 512 elements.  client_ids [clients]
+// int64 and elem_base (the tensor's offset in the flat master) index the
+// uniform draws of key (k0, k1).  The ids' range is checked here, which
+// reads them back (a device sync), unless the caller has checked it:
+// fused.weighted_delta_accum_quant does so once for all its launches.
+void delta_accum_quant(at::Tensor delta, at::Tensor buf, at::Tensor master,
+                       at::Tensor weights, at::Tensor client_ids,
+                       int64_t clients, int64_t bits, int64_t k0, int64_t k1,
+                       int64_t elem_base, bool ids_checked) {
+  TORCH_CHECK(bits == 2 || bits == 4 || bits == 8,
+              "delta_accum_quant: bits ", bits, " not one of 2, 4, 8");
+  TORCH_CHECK(delta.is_cuda() && delta.scalar_type() == at::kFloat &&
+                  delta.is_contiguous(),
+              "delta_accum_quant: delta must be contiguous fp32 on the GPU");
+  TORCH_CHECK(buf.is_cuda() && master.is_cuda() &&
+                  buf.device() == delta.device() &&
+                  master.device() == delta.device() && buf.is_contiguous() &&
+                  master.is_contiguous() &&
+                  buf.scalar_type() == master.scalar_type(),
+              "delta_accum_quant: buf and master must be contiguous, of one "
+              "dtype, on the GPU of delta");
+  // client tiles of 64 are the grid's y dimension
+  TORCH_CHECK(clients >= 1 && clients <= 65535 * 64,
+              "delta_accum_quant: clients ", clients, " outside 1..",
+              65535 * 64);
+  TORCH_CHECK(weights.is_cuda() && weights.device() == delta.device() &&
+                  weights.scalar_type() == at::kFloat &&
+                  weights.is_contiguous() && weights.numel() == clients,
+              "delta_accum_quant: weights must be contiguous fp32 [clients] "
+              "on the GPU of delta");
+  TORCH_CHECK(client_ids.is_cuda() && client_ids.device() == delta.device() &&
+                  client_ids.scalar_type() == at::kLong &&
+                  client_ids.is_contiguous() &&
+                  client_ids.numel() == clients,
+              "delta_accum_quant: client_ids must be contiguous int64 "
+              "[clients] on the GPU of delta");
+  const int64_t n = master.numel();
+  TORCH_CHECK(delta.numel() == n, "delta_accum_quant: delta has ",
+              delta.numel(), " elements, master ", n);
+  TORCH_CHECK(buf.numel() == clients * n, "delta_accum_quant: buf has ",
+              buf.numel(), " elements, expected ", clients, " x ", n);
+  const int64_t lim = (int64_t)1 << 32;
+  TORCH_CHECK(k0 >= 0 && k0 < lim && k1 >= 0 && k1 < lim,
+              "delta_accum_quant: k0 and k1 must be 32-bit words");
+  // the pair index (elem_base + q) / 2 is hashed as a 32-bit word
+  TORCH_CHECK(elem_base >= 0 && elem_base <= 2 * lim - n,
+              "delta_accum_quant: elem_base ", elem_base, " + n ", n,
+              " outside 0..2^33");
+  TORCH_CHECK(buf.scalar_type() == at::kFloat ||
+                  buf.scalar_type() == at::kBFloat16 ||
+                  buf.scalar_type() == at::kHalf,
+              "delta_accum_quant: buf must be fp32, bf16 or fp16, got ",
+              buf.scalar_type());
+  const int dt = dtype_code(buf);
+  if (!ids_checked) {
+    const auto [lo, hi] = at::aminmax(client_ids);
+    TORCH_CHECK(lo.item<int64_t>() >= 0 && hi.item<int64_t>() < lim,
+                "delta_accum_quant: client ids must lie in 0..2^32-1");
+  }
+  if (n == 0) return;
+  ols_delta_accum_quant(delta.data_ptr<float>(), buf.data_ptr(),
+                        master.data_ptr(), weights.data_ptr<float>(),
+                        client_ids.data_ptr<int64_t>(), clients, n, elem_base,
+                        (int)bits, (uint32_t)k0, (uint32_t)k1, dt,
+                        at::cuda::getCurrentCUDAStream().stream());
+}
+
+// "v8" or "scalar": the kernel one quantised accumulate over n elements
+// runs.  dtype 0 fp32, 1 bf16, 2 fp16; the two flags say whether master
+// and buf start on a 16-byte boundary.  Same host function the launcher
+// switches on (uplink_route.h).
+std::string delta_accum_quant_route(int64_t n, int64_t clients, int64_t dtype,
+                                    bool master_aligned, bool buf_aligned) {
+  TORCH_CHECK(n >= 0 && clients >= 1 && dtype >= 0 && dtype <= 2,
+              "delta_accum_quant_route: n >= 0, clients >= 1, dtype 0..2");
+  return ols_delta_accum_quant_route(n, clients, (int)dtype, master_aligned,
+                                     buf_aligned);
+}
+
 // ---- server optimiser step (server_opt.hip) ------------------------------
 // kind 0 momentum, 1 adagrad, 2 adam, 3 yogi.  x (master), m and v are
 // updated in place; momentum has no v and takes an empty one.  z is the
@@ -948,6 +1031,12 @@ TORCH_LIBRARY(olsim_hip, m) {
   m.def("sqnorm_tiles(int n, int clients, int vec) -> int", &sqnorm_tiles);
   m.def("clip_weights(Tensor sq, Tensor weights, float clip_norm) -> "
         "(Tensor, Tensor)");
+  m.def("delta_accum_quant(Tensor(a!) delta, Tensor buf, Tensor master, "
+        "Tensor weights, Tensor client_ids, int clients, int bits, int k0, "
+        "int k1, int elem_base, bool ids_checked=False) -> ()");
+  m.def("delta_accum_quant_route(int n, int clients, int dtype, "
+        "bool master_aligned, bool buf_aligned) -> str",
+        &delta_accum_quant_route);
   m.def("server_opt_step(int kind, Tensor(a!) x, Tensor d, Tensor(b!) m, "
         "Tensor(c!) v, Tensor? z, float total_weight, float sigma, float lr, "
         "float beta1, float beta2, float tau) -> ()");
@@ -1007,6 +1096,7 @@ TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("weighted_delta_accum_flat_dw", &weighted_delta_accum_flat_dw);
   m.impl("client_delta_sqnorm", &client_delta_sqnorm);
   m.impl("clip_weights", &clip_weights);
+  m.impl("delta_accum_quant", &delta_accum_quant);
   m.impl("server_opt_step", &server_opt_step);
   m.impl("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.impl("groupnorm_fwd", &groupnorm_fwd);

@@ -40,6 +40,25 @@ extern "C" void ols_clip_weights(const float* sq, const float* weights,
                                  int64_t clients, float clip,
                                  hipStream_t stream);
 
+// uplink_quant.hip: delta[q] += sum_c weights[c] * Q_bits(buf[c,q] -
+// master[q]) over one parameter tensor of n elements, Q the stochastic
+// bucketed quantiser with 2^(bits-1) - 1 levels per sign (bits 2, 4 or
+// 8).  cids: the clients' ids, elem_base: the tensor's offset in the flat
+// master; with the key (k0, k1) they index the uniform draws, and every
+// cid and (elem_base + n) / 2 must be below 2^32.
+extern "C" void ols_delta_accum_quant(float* delta, const void* buf,
+                                      const void* master,
+                                      const float* weights,
+                                      const int64_t* cids, int64_t clients,
+                                      int64_t n, int64_t elem_base, int bits,
+                                      uint32_t k0, uint32_t k1, int dtype,
+                                      hipStream_t stream);
+// "v8" or "scalar": the kernel that launch runs (uplink_route.h), given
+// whether master and buf start on 16-byte boundaries
+extern "C" const char* ols_delta_accum_quant_route(int64_t n, int64_t clients,
+                                                   int dtype, int master_16b,
+                                                   int buf_16b);
+
 // server_opt.hip: one server optimiser step over the flat fp32 master.
 // kind 0 momentum, 1 adagrad, 2 adam, 3 yogi (server_opt_route.h);
 // x, m, v in place, v unused (may be null) for momentum, z null for no

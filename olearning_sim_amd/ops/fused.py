@@ -8,6 +8,9 @@ aggregation tail of every local-train step:
 - fused_sgd_update:      w_c -= lr * (g_c + mu * (w_c - w_global))
                          (mu=0 -> FedAvg local SGD; mu>0 -> FedProx)
 - weighted_delta_accum:  delta += sum_c alpha_c * (w_c - w_global)
+- weighted_delta_accum_quant: the same sum over updates quantised to 2, 4
+                         or 8 bits per weight as they are read (uplink
+                         compression)
 - apply_aggregate:       w_global += delta / total_weight  (fp32 master)
 - server_opt_step:       FedAvgM / FedAdagrad / FedAdam / FedYogi step on
                          the fp32 master with g = delta / total_weight
@@ -203,6 +206,164 @@ def clip_weights(sq: torch.Tensor, weights: torch.Tensor, clip_norm: float):
         s = torch.where(sq > S * S, S / sq.sqrt(), torch.ones_like(sq))
         w_eff = weights.float() * s
         return w_eff, w_eff.sum().reshape(1)
+
+
+# -- uplink compression -----------------------------------------------------
+#
+# Each client's update is quantised to `bits` bits per weight before it is
+# aggregated: per parameter tensor and per bucket of UPLINK_BUCKET
+# consecutive elements, with L = 2^(bits-1) - 1 levels per sign,
+#
+#   d = f32(client) - f32(global)            a = max |d| over the bucket
+#   t = |d| * L / a                          l = min(L, floor(t) + [u < frac(t)])
+#   Q = sign(d) * l * (a / L)                (a == 0: Q = 0)
+#
+# u is 16 bits of a counter hash of (key, client id, element index in the
+# flat master): uplink_uniform.  The quantiser is unbiased, E[Q] = d.
+
+UPLINK_BUCKET = 512
+UPLINK_BITS = (2, 4, 8)
+_M32 = 0xFFFFFFFF
+
+
+def uplink_levels(bits: int) -> int:
+    if bits not in UPLINK_BITS:
+        raise ValueError(f"uplink bits {bits!r} not one of {UPLINK_BITS}")
+    return (1 << (bits - 1)) - 1
+
+
+def _mul32(x: torch.Tensor, k: int) -> torch.Tensor:
+    """x * k mod 2^32 on an int64 tensor of 32-bit words, formed from
+    16-bit halves: a 32 x 32 bit product does not fit int64."""
+    lo = (x & 0xFFFF) * k
+    hi = ((x >> 16) * (k & 0xFFFF)) & 0xFFFF
+    return (lo + (hi << 16)) & _M32
+
+
+def _fmix32(h: torch.Tensor) -> torch.Tensor:
+    """murmur3's 32-bit finaliser on int64 tensors holding 32-bit words."""
+    h = h ^ (h >> 16)
+    h = _mul32(h, 0x85EBCA6B)
+    h = h ^ (h >> 13)
+    h = _mul32(h, 0xC2B2AE35)
+    return h ^ (h >> 16)
+
+
+def uplink_key(seed: int, round_idx: int, rank: int) -> int:
+    """The 64-bit key of one rank's draws in one round.  The rank enters
+    because client ids are per-rank shards; the round, so that a resumed
+    run draws what it would have drawn."""
+    return (seed * 1_000_003 + round_idx * 7919 + rank * 2_654_435_761
+            + 0xC0DEC) % (1 << 64)
+
+
+def uplink_words(key: int, client_ids: torch.Tensor,
+                 p: torch.Tensor) -> torch.Tensor:
+    """The 32-bit hash word of every (client, element pair p) as int64
+    [C, len(p)]: fmix32(ckey ^ (p * 0x9E3779B9)) with ckey =
+    fmix32(fmix32(k0 ^ cid) ^ k1), (k0, k1) the low and high words of
+    key.  client_ids and p are integer tensors of values below 2^32."""
+    k0, k1 = key & _M32, (key >> 32) & _M32
+    cid = client_ids.to(torch.int64).reshape(-1, 1)
+    p = p.to(torch.int64).reshape(1, -1)
+    ckey = _fmix32(_fmix32(cid ^ k0) ^ k1)
+    return _fmix32(ckey ^ _mul32(p, 0x9E3779B9))
+
+
+def uplink_uniform(key: int, client_ids: torch.Tensor,
+                   j: torch.Tensor) -> torch.Tensor:
+    """u in [0, 1) as fp32 [C, len(j)], a multiple of 2^-16: the uniform
+    that client client_ids[c] draws for the element at index j of the flat
+    master under key.  One hash word serves the pair (2p, 2p+1): the even
+    element takes its low half, the odd one its high half."""
+    j = j.to(torch.int64).reshape(-1)
+    word = uplink_words(key, client_ids, j >> 1)
+    half = torch.where((j & 1).reshape(1, -1) == 0, word & 0xFFFF, word >> 16)
+    return half.to(torch.float32) / 65536.0
+
+
+def uplink_bytes_per_client(numels: Sequence[int], bits: int) -> int:
+    """Bytes one client's compressed update puts on the wire: the packed
+    levels plus one fp32 scale per bucket, summed over parameter tensors."""
+    uplink_levels(bits)
+    return sum((n * bits + 7) // 8
+               + 4 * ((n + UPLINK_BUCKET - 1) // UPLINK_BUCKET)
+               for n in numels)
+
+
+def _quantise_eager(diff: torch.Tensor, u: torch.Tensor,
+                    levels: int) -> torch.Tensor:
+    """Q of the contract for fp32 diff [C, n] and uniforms u [C, n]."""
+    C, n = diff.shape
+    pad = (-n) % UPLINK_BUCKET
+    d = torch.nn.functional.pad(diff, (0, pad)).view(C, -1, UPLINK_BUCKET)
+    a = d.abs().amax(dim=2, keepdim=True)
+    L = float(levels)
+    safe = torch.where(a == 0, torch.ones_like(a), a)
+    t = d.abs() * L / safe
+    fl = t.floor()
+    up = torch.nn.functional.pad(u, (0, pad)).view_as(d)
+    lvl = torch.minimum(fl + (up < t - fl).float(), torch.full_like(t, L))
+    q = torch.sign(d) * lvl * (a / L)
+    return q.view(C, -1)[:, :n]
+
+
+def weighted_delta_accum_quant(delta: Sequence[torch.Tensor],
+                               client_params: Sequence[torch.Tensor],
+                               global_params: Sequence[torch.Tensor],
+                               weights: torch.Tensor,
+                               client_ids: torch.Tensor, bits: int, key: int,
+                               elem_offsets: Sequence[int]) -> None:
+    """delta[i] (fp32) += sum_c weights[c] * Q(client_params[i][c] -
+    global_params[i]): weighted_delta_accum over updates quantised to
+    `bits` bits per weight (2, 4 or 8; the rule above).
+
+    client_ids [C] int64: the clients' ids; key: uplink_key's 64-bit
+    value; elem_offsets[i]: where global_params[i] starts in the flat
+    master.  Ids and pair indices are hashed as 32-bit words: every id and
+    every (elem_offsets[i] + numel) / 2 must be below 2^32.
+
+    GPU: one launch per parameter (csrc/uplink_quant.hip), deterministic
+    below 64 clients.  CPU: the same rule in fp32 torch ops."""
+    levels = uplink_levels(bits)
+    if not delta:
+        return
+    key = int(key) % (1 << 64)
+    for off, gw in zip(elem_offsets, global_params):
+        if off < 0 or off + gw.numel() > (1 << 33):
+            raise ValueError("uplink quantiser: element index "
+                             f"{off + gw.numel()} past 2^33")
+    if client_params[0].is_cuda:
+        ops = load_hip_ops(required=True)
+        C = client_params[0].shape[0]
+        w = weights.float().contiguous()
+        cid = client_ids.to(torch.int64).contiguous()
+        # one host read for all the launches
+        lo, hi = (int(x) for x in torch.aminmax(cid))
+        if lo < 0 or hi > _M32:
+            raise ValueError("uplink quantiser: client ids must lie in "
+                             "0..2^32-1")
+        for dl, cw, gw, off in zip(delta, client_params, global_params,
+                                   elem_offsets):
+            ops.delta_accum_quant(dl.reshape(-1), cw.detach().reshape(-1),
+                                  gw.detach().reshape(-1), w, cid, C,
+                                  int(bits), key & _M32, (key >> 32) & _M32,
+                                  int(off), True)
+        return
+    with torch.no_grad():
+        ids = client_ids.to(torch.int64).cpu()
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) > _M32):
+            raise ValueError("uplink quantiser: client ids must lie in "
+                             "0..2^32-1")
+        C = ids.numel()
+        w = weights.float().view(C, 1)
+        for dl, cw, gw, off in zip(delta, client_params, global_params,
+                                   elem_offsets):
+            n = gw.numel()
+            diff = cw.float().reshape(C, n) - gw.float().reshape(1, n)
+            u = uplink_uniform(key, ids, off + torch.arange(n))
+            q = _quantise_eager(diff, u, levels)
+            dl.reshape(-1).add_((q * w).sum(dim=0))
 
 
 def apply_aggregate(global_params: Sequence[torch.Tensor],

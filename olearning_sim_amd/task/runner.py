@@ -18,7 +18,7 @@ Operator knobs come from the train operator's `operator_params` JSON
 model, lr, local_steps, batch_size, prox_mu, cohort_size, num_classes,
 dirichlet_alpha, dtype, chunk_clients, vocab_size, seq_len, clip_norm,
 noise_multiplier, update_norm_stats, server_optimizer, server_lr,
-server_beta1, server_beta2, server_tau.
+server_beta1, server_beta2, server_tau, uplink_bits.
 """
 
 from __future__ import annotations
@@ -136,6 +136,7 @@ def engine_job_from_task(task: TaskConfig, allocations: List[DataAllocation],
         server_beta1=float(params.get("server_beta1", 0.9)),
         server_beta2=float(params.get("server_beta2", 0.99)),
         server_tau=float(params.get("server_tau", 1e-3)),
+        uplink_bits=int(params.get("uplink_bits", 0)),
         dtype=params.get("dtype", "float32" if device == "cpu" else "bfloat16"),
         device=device,
         chunk_clients=params.get("chunk_clients", 0),
