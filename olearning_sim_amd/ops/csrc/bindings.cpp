@@ -652,15 +652,14 @@ void sgd_conv3_wt(at::Tensor w, at::Tensor g, at::Tensor wt, double lr) {
 // ntab: int32 [B*OH*OW] plane offsets (b*H*W + oh*W + ow) built host-side
 
 // Which kernel a [*, IC, *, H, W] x and OC output channels run in
-// direction dir ("fwd", "dgrad", "wgrad"): "direct", "mfma" or
-// "two_stage".  Same host functions the launchers branch on; reads
-// OLSIM_CONV5 on every call.
+// direction dir ("fwd", "dgrad", "wgrad"): "direct" or "mfma".  Same host
+// functions the launchers branch on; reads OLSIM_CONV5 on every call.
 std::string conv5x5_route(std::string dir, int64_t IC, int64_t OC, int64_t H,
                           int64_t W) {
   int d = dir == "fwd" ? 0 : dir == "dgrad" ? 1 : dir == "wgrad" ? 2 : -1;
   TORCH_CHECK(d >= 0, "conv5x5_route: dir must be fwd, dgrad or wgrad");
   int r = ols_conv5x5_route(d, (int)IC, (int)OC, (int)H, (int)W);
-  return r == 0 ? "direct" : r == 1 ? "mfma" : "two_stage";
+  return r == 0 ? "direct" : "mfma";
 }
 
 // ntab has one int32 per position of the plane the kernel tiles over
@@ -705,17 +704,7 @@ at::Tensor conv5x5_wgrad(at::Tensor x, at::Tensor dy, at::Tensor ntab) {
   TORCH_CHECK(d.OC <= 16 && nq % 32 == 0);
   check_ntab(ntab, x, nq);
   auto dw = at::empty({d.C, d.OC, d.IC, 5, 5}, x.options());
-  // The two-stage route (client_conv5.hip k_conv5x5_wgrad_part) needs a
-  // [C, B, ntaps] fp32 partial buffer; the launcher takes that route
-  // exactly when it gets one.
-  at::Tensor part;
-  float* partp = nullptr;
-  if (ols_conv5x5_route(2, d.IC, d.OC, d.H, d.W) == 2) {
-    part = at::empty({(int64_t)d.C * d.B * d.OC * d.IC * 25},
-                     x.options().dtype(at::kFloat));
-    partp = part.data_ptr<float>();
-  }
-  ols_conv5x5_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), partp,
+  ols_conv5x5_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
                     ntab.data_ptr<int>(), d.C, d.IC, d.OC, d.B, d.H, d.W,
                     at::cuda::getCurrentCUDAStream().stream());
   return dw;

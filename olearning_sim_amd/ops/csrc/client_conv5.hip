@@ -339,9 +339,9 @@ static inline int xcd_blocks5(int C, int T) { return ((C + 7) / 8 * 8) * T; }
 // Route decisions, one host function per direction.  The launchers below
 // and the binding's conv5x5_route() both go through these, so a test can
 // assert the kernel a shape runs.  OLSIM_CONV5 is read on every call:
-// "mfma" forces the implicit-GEMM kernels, "direct" additionally selects
-// the two-stage weight gradient.  H, W are the x plane in all three.
-enum { CV5_DIRECT = 0, CV5_MFMA = 1, CV5_TWO_STAGE = 2 };
+// a value starting with 'm' ("mfma") forces the implicit-GEMM kernels.
+// H, W are the x plane in all three.
+enum { CV5_DIRECT = 0, CV5_MFMA = 1 };
 #define CV5_DIRECT_LDS 32768
 
 static inline char conv5_env() {
@@ -362,12 +362,6 @@ static inline size_t conv5_dgrad_direct_lds(int IC, int OC, int H, int W) {
          * sizeof(short);
 }
 
-// two-stage wgrad stage 1: the x planes plus the dy planes of one image
-static inline size_t conv5_wgrad_part_lds(int IC, int OC, int H, int W) {
-  return ((size_t)IC * H * W + (size_t)OC * (H - 4) * (W - 4))
-         * sizeof(short);
-}
-
 static int conv5_route_fwd(int IC, int OC, int H, int W) {
   // the register-blocked kernel reads x rows as u32 pairs: W even, and
   // its 4-wide column blocks need OW >= 4
@@ -385,10 +379,8 @@ static int conv5_route_dgrad(int IC, int OC, int H, int W) {
   return CV5_MFMA;
 }
 
+// the weight gradient has the implicit-GEMM kernel only
 static int conv5_route_wgrad(int IC, int OC, int H, int W) {
-  if (conv5_wgrad_part_lds(IC, OC, H, W) <= CV5_DIRECT_LDS
-      && conv5_env() == 'd')
-    return CV5_TWO_STAGE;
   return CV5_MFMA;
 }
 
@@ -633,116 +625,14 @@ extern "C" void ols_conv5x5_dgrad(const void* dyp, const void* w, void* dx,
                      (__hip_bfloat16*)dx, ntab, g);
 }
 
-
-
-// Two-stage direct wgrad (default): stage 1 computes per-(client, b)
-// fp32 tap partials — grid C*B keeps the chip full and each tap's
-// q-loop is only OH*OW deep (the single-stage per-client version
-// measured ~2x slower: C-only grid + 1600-deep serial chains).
-// Stage 2 reduces the B partials and stores bf16.
-__global__ __launch_bounds__(CV5_THREADS) void k_conv5x5_wgrad_part(
-    const __hip_bfloat16* __restrict__ x, const __hip_bfloat16* __restrict__ dy,
-    float* __restrict__ part, ConvGeom5 g) {
-  const int c = blockIdx.x / g.B;
-  const int b = blockIdx.x - c * g.B;
-  const int HW = g.H * g.W, OHW = g.OH * g.OW;
-  const int K = g.IC * 25;
-  const int ntaps = g.OC * K;
-  extern __shared__ __attribute__((aligned(16))) short smem[];
-  short* x_lds = smem;                          // [IC*HW]
-  short* d_lds = smem + g.IC * HW;              // [OC*OHW]
-  const ushort* xc = reinterpret_cast<const ushort*>(x)
-                     + ((int64_t)c * g.IC * g.B + b) * HW;
-  const ushort* dc = reinterpret_cast<const ushort*>(dy)
-                     + ((int64_t)c * g.OC * g.B + b) * OHW;
-  for (int ic = 0; ic < g.IC; ++ic) {
-    const ushort* plane = xc + (int64_t)ic * g.B * HW;
-    for (int i = threadIdx.x; i < HW; i += CV5_THREADS)
-      x_lds[ic * HW + i] = (short)plane[i];
-  }
-  for (int oc = 0; oc < g.OC; ++oc) {
-    const ushort* plane = dc + (int64_t)oc * g.B * OHW;
-    for (int i = threadIdx.x; i < OHW; i += CV5_THREADS)
-      d_lds[oc * OHW + i] = (short)plane[i];
-  }
-  __syncthreads();
-  float* pout = part + ((int64_t)c * g.B + b) * ntaps;
-  for (int tap = threadIdx.x; tap < ntaps; tap += CV5_THREADS) {
-    const int oc = tap / K;
-    const int r = tap - oc * K;
-    const int ic = r / 25, rr = r - ic * 25;
-    const int dh = rr / 5, dw2 = rr - dh * 5;
-    const short* dr = d_lds + oc * OHW;
-    const short* xr = x_lds + ic * HW + dh * g.W + dw2;
-    float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-    for (int oh = 0; oh < g.OH; ++oh) {
-      const short* drow = dr + oh * g.OW;
-      const short* xrow = xr + oh * g.W;
-      int ow = 0;
-      for (; ow + 4 <= g.OW; ow += 4) {
-        ushort d0 = (ushort)drow[ow], x0 = (ushort)xrow[ow];
-        ushort d1 = (ushort)drow[ow + 1], x1 = (ushort)xrow[ow + 1];
-        ushort d2 = (ushort)drow[ow + 2], x2 = (ushort)xrow[ow + 2];
-        ushort d3 = (ushort)drow[ow + 3], x3 = (ushort)xrow[ow + 3];
-        p0 += to_f32(*reinterpret_cast<__hip_bfloat16*>(&d0))
-              * to_f32(*reinterpret_cast<__hip_bfloat16*>(&x0));
-        p1 += to_f32(*reinterpret_cast<__hip_bfloat16*>(&d1))
-              * to_f32(*reinterpret_cast<__hip_bfloat16*>(&x1));
-        p2 += to_f32(*reinterpret_cast<__hip_bfloat16*>(&d2))
-              * to_f32(*reinterpret_cast<__hip_bfloat16*>(&x2));
-        p3 += to_f32(*reinterpret_cast<__hip_bfloat16*>(&d3))
-              * to_f32(*reinterpret_cast<__hip_bfloat16*>(&x3));
-      }
-      for (; ow < g.OW; ++ow) {
-        ushort d0 = (ushort)drow[ow], x0 = (ushort)xrow[ow];
-        p0 += to_f32(*reinterpret_cast<__hip_bfloat16*>(&d0))
-              * to_f32(*reinterpret_cast<__hip_bfloat16*>(&x0));
-      }
-    }
-    pout[tap] = (p0 + p1) + (p2 + p3);
-  }
-}
-
-__global__ __launch_bounds__(OLS_THREADS) void k_conv5x5_wgrad_reduce(
-    const float* __restrict__ part, __hip_bfloat16* __restrict__ dw,
-    int64_t C, int B, int ntaps) {
-  const int64_t total = C * ntaps;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       u < total; u += stride) {
-    const int64_t c = u / ntaps;
-    const int tap = (int)(u - c * ntaps);
-    const float* p = part + c * B * (int64_t)ntaps + tap;
-    float acc = 0.f;
-    for (int b = 0; b < B; ++b) acc += p[(int64_t)b * ntaps];
-    dw[u] = __float2bfloat16(acc);
-  }
-}
-
 extern "C" void ols_conv5x5_wgrad(const void* x, const void* dy, void* dw,
-                                  float* part, const int* ntab, int C,
-                                  int IC, int OC, int B, int H, int W,
-                                  hipStream_t stream) {
+                                  const int* ntab, int C, int IC, int OC,
+                                  int B, int H, int W, hipStream_t stream) {
   ConvGeom5 g;
   g.B = B; g.H = H; g.W = W; g.OH = H - 4; g.OW = W - 4;
   g.IC = IC; g.OC = OC; g.C = C;
   g.K = 0; g.KP = 0;
   g.tiles_n = cdiv5(IC * 25, CV5_BN);
-  if (part != nullptr && conv5_route_wgrad(IC, OC, H, W) == CV5_TWO_STAGE) {
-    // two-stage direct path: the binding allocates the [C, B, ntaps] fp32
-    // partial buffer exactly when conv5_route_wgrad says two-stage
-    const size_t lds1 = conv5_wgrad_part_lds(IC, OC, H, W);
-    hipLaunchKernelGGL(k_conv5x5_wgrad_part, dim3((unsigned)((int64_t)C * B)),
-                       dim3(CV5_THREADS), lds1, stream,
-                       (const __hip_bfloat16*)x, (const __hip_bfloat16*)dy,
-                       part, g);
-    const int ntaps = OC * IC * 25;
-    hipLaunchKernelGGL(k_conv5x5_wgrad_reduce,
-                       dim3(ols_grid((int64_t)C * ntaps, OLS_THREADS)),
-                       dim3(OLS_THREADS), 0, stream, part,
-                       (__hip_bfloat16*)dw, (int64_t)C, B, ntaps);
-    return;
-  }
   dim3 grid(xcd_blocks5(C, g.tiles_n));
   hipLaunchKernelGGL(k_conv5x5_wgrad, grid, dim3(CV5_THREADS), 0, stream,
                      (const __hip_bfloat16*)x, (const __hip_bfloat16*)dy,

@@ -8,7 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
-// name<template arguments> as conv3x3_route() spells it.  fwd_v6/v7/v8
+// name<template arguments> as conv3x3_route() spells it.  fwd_v6/v7
 // carry <LG_OW, STRIDE>, dgrad_v6/v7 <LG_OW>, dgrad_s2 <LG_OW> (its four
 // parity-class launches share it), fwd_v5 <ROW_HOIST>, dgrad_v5 <STRIDE>.
 #define CONV3_ROUTES(X)                                                     \
@@ -22,9 +22,6 @@
   X(FWD_V6_3_2, "fwd_v6<3,2>") X(FWD_V6_4_2, "fwd_v6<4,2>")                 \
   X(FWD_V7_3_1, "fwd_v7<3,1>") X(FWD_V7_4_1, "fwd_v7<4,1>")                 \
   X(FWD_V7_5_1, "fwd_v7<5,1>")                                              \
-  X(FWD_V8_2_1, "fwd_v8<2,1>") X(FWD_V8_3_1, "fwd_v8<3,1>")                 \
-  X(FWD_V8_4_1, "fwd_v8<4,1>") X(FWD_V8_2_2, "fwd_v8<2,2>")                 \
-  X(FWD_V8_3_2, "fwd_v8<3,2>") X(FWD_V8_4_2, "fwd_v8<4,2>")                 \
   X(DGRAD_V6_2, "dgrad_v6<2>") X(DGRAD_V6_3, "dgrad_v6<3>")                 \
   X(DGRAD_V6_4, "dgrad_v6<4>")                                              \
   X(DGRAD_V7_2, "dgrad_v7<2>") X(DGRAD_V7_3, "dgrad_v7<3>")                 \
@@ -49,21 +46,20 @@ static inline const char* conv3_route_name(Conv3Route r) {
   return names[r];
 }
 
-// The six A/B switches, read on every call.  OLSIM_CONV_V=5 sends every
-// shape to the v5 family; the other five act on presence, whatever the
+// The five A/B switches, read on every call.  OLSIM_CONV_V=5 sends every
+// shape to the v5 family; the other four act on presence, whatever the
 // value (OLSIM_CONV_DW8=0 restores the scalar wgrad gather because it is
-// set): OLSIM_CONV_V8 the two-ahead fwd_v8, OLSIM_CONV_DW64 the BK=64
-// dgrad_v7 / wgrad_v7, OLSIM_CONV_DW8 no run-vectorised wgrad_v8 / v8s,
+// set): OLSIM_CONV_DW64 the BK=64 dgrad_v7 / wgrad_v7,
+// OLSIM_CONV_DW8 no run-vectorised wgrad_v8 / v8s,
 // OLSIM_CONV_NMAJOR the [n][k] B tile in every fwd / dgrad kernel,
 // OLSIM_CONV_BM64 the 64x128 block tile in every forward kernel.
 struct Conv3Env {
-  bool v5, v8, dw64, no_dw8, nmajor, bm64;
+  bool v5, dw64, no_dw8, nmajor, bm64;
 };
 
 static inline Conv3Env conv3_env() {
   const char* v = getenv("OLSIM_CONV_V");
   return {v != nullptr && strcmp(v, "5") == 0,
-          getenv("OLSIM_CONV_V8") != nullptr,
           getenv("OLSIM_CONV_DW64") != nullptr,
           getenv("OLSIM_CONV_DW8") != nullptr,
           getenv("OLSIM_CONV_NMAJOR") != nullptr,
@@ -140,12 +136,7 @@ static inline Conv3Route conv3_route_fwd_v6(int IC, int OC, int B, int H,
       {CV3_FWD_V6_2_2, CV3_FWD_V6_3_2, CV3_FWD_V6_4_2}};
   static const Conv3Route v7[3] = {CV3_FWD_V7_3_1, CV3_FWD_V7_4_1,
                                    CV3_FWD_V7_5_1};
-  static const Conv3Route v8[2][3] = {
-      {CV3_FWD_V8_2_1, CV3_FWD_V8_3_1, CV3_FWD_V8_4_1},
-      {CV3_FWD_V8_2_2, CV3_FWD_V8_3_2, CV3_FWD_V8_4_2}};
   const int lg_ow = conv3_lg(conv3_cdiv(W, stride));
-  // OLSIM_CONV_V8 forces the two-ahead BK=32 pipeline everywhere (A/B)
-  if (conv3_env().v8) return v8[stride != 1][conv3_clamp(lg_ow, 2, 4) - 2];
   // BK=64 (v7) wins +5..10% at OW >= 8 stride 1 (A/B at C=250); the
   // 4x4-plane deep layers and stride 2 measured flat-to-worse, so they
   // stay on BK=32.
@@ -188,7 +179,7 @@ static inline Conv3Route conv3_route_wgrad_v6(int IC, int OC, int B, int H,
 // <LG_OW, STRIDE> stay the route's; the staging is one more template
 // argument.  Only the stride-1 fwd_v6 / fwd_v7 / dgrad_v6 kernels have the
 // k-major form: at stride 2 a thread's columns are alternate elements,
-// and fwd_v8 / dgrad_v7 are records kept as they were measured.
+// and dgrad_v7 is a record kept as it was measured.
 // fwd_v7<3,1> (OW = 8, the 256-channel stage) stays [n][k]: k-major
 // measured 1.3 % slower there (0.850 vs 0.839 ms at C=250,
 // profiles/conv_kmajor_r06.md), so it has no k-major instantiation.
@@ -210,9 +201,9 @@ static inline bool conv3_kmajor_v6(int dir, Conv3Route r) {
 // per MFMA).  Like the staging, one more template argument that the route
 // name does not carry.  fwd_v6<*,1>, fwd_v6<*,2> and fwd_v7<*,1> take the
 // taller tile when it adds no padded rows (OC = 96, 128, 256, 512 ...; not
-// 64 or 192); fwd_v8 is a record kept as measured, and the dgrad / wgrad
-// kernels have the one tile.  The flipped-weight dgrad runs the forward of
-// (OC, IC) and so gets that forward's tile.
+// 64 or 192); the dgrad / wgrad kernels have the one tile.  The
+// flipped-weight dgrad runs the forward of (OC, IC) and so gets that
+// forward's tile.
 // All nine instantiations measured faster on the taller tile (C=250, B=16,
 // OLSIM_CONV_BM64 set against unset, profiles/conv_tile_r08.md): stride 2
 // +30 %, fwd_v7<3,1> +7.2 %, fwd_v7<4,1> +4.7 %, fwd_v7<5,1> +3.8 %,

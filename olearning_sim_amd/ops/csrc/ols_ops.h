@@ -135,9 +135,8 @@ extern "C" void ols_conv5x5_dgrad(const void* dyp, const void* w, void* dx,
                                   int B, int H, int W, hipStream_t stream);
 extern "C" int ols_conv5x5_route(int dir, int IC, int OC, int H, int W);
 extern "C" void ols_conv5x5_wgrad(const void* x, const void* dy, void* dw,
-                                  float* part, const int* ntab, int C,
-                                  int IC, int OC, int B, int H, int W,
-                                  hipStream_t stream);
+                                  const int* ntab, int C, int IC, int OC,
+                                  int B, int H, int W, hipStream_t stream);
 
 extern "C" void ols_pool2x2_fwd(const void* x, void* y, unsigned char* arg,
                                 int64_t planes, int OH, int OW, int dtype,

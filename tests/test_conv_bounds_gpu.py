@@ -72,7 +72,7 @@ def _check_conv3x3(shape, v6, tag, routes, forced_v5=False):
 
 
 # The expected routes below were read off the launchers' branches by hand
-# (fwd_v6/v7/v8<LG_OW,STRIDE>, dgrad_v6/v7/s2<LG_OW> with LG_OW = log2(OW)
+# (fwd_v6/v7<LG_OW,STRIDE>, dgrad_v6/v7/s2<LG_OW> with LG_OW = log2(OW)
 # clamped to the instantiated range), not produced by conv3x3_route.
 
 # (C, IC, OC, B, H, W, stride) of the v6 padded family -> (fwd, dgrad,
@@ -102,22 +102,7 @@ V6_ROUTES = {
 }
 V6_SHAPES = list(V6_ROUTES)
 
-# what a variable changes in V6_ROUTES.  OLSIM_CONV_V8: every forward is
-# fwd_v8, LG_OW clamped to 2..4, before v7 is considered.
-V8_FWD = {
-    (1, 64, 64, 1, 32, 32, 1): "fwd_v8<4,1>",
-    (2, 64, 64, 2, 8, 16, 1): "fwd_v8<4,1>",
-    (2, 64, 64, 2, 16, 8, 1): "fwd_v8<3,1>",
-    (2, 64, 64, 2, 4, 32, 1): "fwd_v8<4,1>",
-    (2, 64, 128, 2, 16, 32, 2): "fwd_v8<4,2>",
-    (2, 64, 96, 2, 4, 4, 1): "fwd_v8<2,1>",
-    (2, 32, 32, 2, 4, 4, 1): "fwd_v8<2,1>",
-    (2, 64, 64, 4, 4, 4, 1): "fwd_v8<2,1>",
-    (2, 64, 128, 4, 8, 8, 2): "fwd_v8<2,2>",
-    (2, 64, 128, 2, 16, 16, 2): "fwd_v8<3,2>",
-    (2, 32, 32, 1, 8, 8, 1): "fwd_v8<3,1>",
-    (2, 32, 32, 1, 16, 16, 1): "fwd_v8<4,1>",
-}
+# what a variable changes in V6_ROUTES.
 # OLSIM_CONV_DW64: dgrad_v7 at stride 1 when OC*9 % 64 == 0 (OC = 96 and
 # 32 are not), LG_OW up to 5; wgrad_v7 when v8 / v8s do not run (OW < 8)
 # and B*OH*OW % 64 == 0.  Shapes not listed keep their V6_ROUTES entry.
@@ -162,8 +147,7 @@ DW8_SHAPES = [
     (2, 64, 128, 2, 16, 32, 2),
 ]
 
-CONV3_VARS = ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
-              "OLSIM_CONV_DW8")
+CONV3_VARS = ("OLSIM_CONV_V", "OLSIM_CONV_DW64", "OLSIM_CONV_DW8")
 
 
 def _conv3_env(monkeypatch, var=None, value="1"):
@@ -185,17 +169,14 @@ def test_conv3x3_v5_family_bounded(shape, monkeypatch):
     _check_conv3x3(shape, False, "conv3.v5", V5_ROUTES[shape])
 
 
-@pytest.mark.parametrize("var", ["OLSIM_CONV_V8", "OLSIM_CONV_DW64"])
+@pytest.mark.parametrize("var", ["OLSIM_CONV_DW64"])
 @pytest.mark.parametrize("shape", V6_SHAPES, ids=str)
 def test_conv3x3_env_gated_kernels_bounded(shape, var, monkeypatch):
-    """fwd_v8 (OLSIM_CONV_V8) and dgrad_v7 / wgrad_v7 (OLSIM_CONV_DW64);
-    the launchers read the environment on every call."""
+    """dgrad_v7 / wgrad_v7 (OLSIM_CONV_DW64); the launchers read the
+    environment on every call."""
     _conv3_env(monkeypatch, var)
     fwd, dgrad, wgrad = V6_ROUTES[shape]
-    if var == "OLSIM_CONV_V8":
-        fwd = V8_FWD[shape]
-    else:
-        dgrad, wgrad = DW64_DGRAD_WGRAD.get(shape, (dgrad, wgrad))
+    dgrad, wgrad = DW64_DGRAD_WGRAD.get(shape, (dgrad, wgrad))
     _check_conv3x3(shape, True, "conv3." + var.rsplit("_", 1)[1].lower(),
                    (fwd, dgrad, wgrad))
 
@@ -220,13 +201,48 @@ def test_conv3x3_forced_v5_kernels_bounded(shape, monkeypatch):
                    forced_v5=True)
 
 
+RETIRED = [("OLSIM_CONV_V8", "1"), ("OLSIM_CONV5", "direct")]
+
+
+@pytest.mark.parametrize("var, value", RETIRED)
+def test_retired_switches_are_ignored(var, value, monkeypatch):
+    """The two settings whose kernels were retired (KERNEL_NOTES.md) change
+    no route: host functions only, no kernel is launched."""
+    from olearning_sim_amd.ops import load_hip_ops
+    from olearning_sim_amd.ops.conv import dgrad_wt_ok
+    ops = load_hip_ops(required=True)
+    conv5_shapes = sorted({case[0] for case in CONV5_CASES})
+
+    def routes():
+        got = {}
+        for shape in V6_SHAPES:
+            C, IC, OC, B, H, W, s = shape
+            got[shape] = tuple(ops.conv3x3_route(d, IC, OC, B, H, W, s)
+                               for d in ("fwd", "dgrad", "wgrad")) \
+                + (dgrad_wt_ok(ops, OC, IC, B, H, W, s),)
+        for shape in conv5_shapes:
+            C, IC, OC, B, H, W = shape
+            got[shape] = tuple(ops.conv5x5_route(d, IC, OC, H, W)
+                               for d in ("fwd", "dgrad", "wgrad"))
+        return got
+
+    _conv3_env(monkeypatch)
+    for other, _ in RETIRED:
+        monkeypatch.delenv(other, raising=False)
+    unset = routes()
+    for shape in V6_SHAPES:
+        assert unset[shape][:3] == V6_ROUTES[shape]
+    monkeypatch.setenv(var, value)
+    assert routes() == unset
+
+
 # ---------------------------------------------------------------------------
 # conv5x5
 
 # (shape, OLSIM_CONV5, expected fwd / dgrad / wgrad route); shapes are
 # (C, IC, OC, B, H, W) with B*(H-4)*(W-4) % 32 == 0.  LDS needs in bytes:
-# fwd 2*(IC*H*W + OC*IC*25), dgrad 2*(OC*(H+4)*(W+4) + OC*IC*25), two-stage
-# wgrad 2*(IC*H*W + OC*(H-4)*(W-4)); the direct limit is 32768.
+# fwd 2*(IC*H*W + OC*IC*25), dgrad 2*(OC*(H+4)*(W+4) + OC*IC*25); the
+# direct limit is 32768.  wgrad has the MFMA kernel only.
 CONV5_CASES = [
     # non-square plane and the IC = OC = 16 limit
     ((2, 4, 8, 2, 12, 20), None, "direct", "direct", "mfma"),
@@ -241,10 +257,6 @@ CONV5_CASES = [
     ((2, 4, 8, 2, 12, 20), "mfma", "mfma", "mfma", "mfma"),
     ((2, 16, 16, 2, 12, 12), "mfma", "mfma", "mfma", "mfma"),
     ((2, 6, 16, 8, 14, 14), "mfma", "mfma", "mfma", "mfma"),
-    ((2, 4, 8, 2, 12, 20), "direct", "direct", "direct", "two_stage"),
-    ((2, 16, 16, 2, 12, 12), "direct", "direct", "direct", "two_stage"),
-    # two-stage wgrad needs 45312 B: back to the MFMA wgrad
-    ((1, 16, 8, 2, 32, 32), "direct", "mfma", "direct", "mfma"),
 ]
 
 
@@ -257,9 +269,7 @@ def _conv5_id(case):
 def test_conv5x5_bounded(case, relu, monkeypatch):
     """Every conv5x5 route, with the route asserted through the host
     functions the launchers branch on (the launchers read OLSIM_CONV5 on
-    every call).  The two-stage weight gradient still reduces over
-    B*OH*OW and the bound covers any summation order, so it needs no term
-    of its own.  ReLU: signs the fp64 pre-activation cannot decide follow
+    every call).  ReLU: signs the fp64 pre-activation cannot decide follow
     the kernel's own mask."""
     from olearning_sim_amd.ops import load_hip_ops
     from olearning_sim_amd.ops.conv import client_conv5x5, conv5x5_supported

@@ -14,9 +14,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
-CONV_VARS = ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
-             "OLSIM_CONV_DW8", "OLSIM_CONV_NMAJOR", "OLSIM_DGRAD_WT",
-             "OLSIM_GN_PAD")
+CONV_VARS = ("OLSIM_CONV_V", "OLSIM_CONV_DW64", "OLSIM_CONV_DW8",
+             "OLSIM_CONV_NMAJOR", "OLSIM_DGRAD_WT", "OLSIM_GN_PAD")
 C = 3       # client stride exercised in every case
 
 # (IC, OC, B, H, W) of the conv whose dgrad it is -> forward route of the

@@ -14,8 +14,8 @@ pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
 DIRS = ("fwd", "dgrad")
-CONV_VARS = ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
-             "OLSIM_CONV_DW8", "OLSIM_CONV_NMAJOR")
+CONV_VARS = ("OLSIM_CONV_V", "OLSIM_CONV_DW64", "OLSIM_CONV_DW8",
+             "OLSIM_CONV_NMAJOR")
 
 # (C, IC, OC, B, H, W, stride) -> the (fwd, dgrad) kernels it reaches
 SHAPES = {
@@ -134,10 +134,7 @@ def test_staging_of_unconverted_kernels(ops, monkeypatch):
     for d in DIRS:
         assert ops.conv3x3_staging(d, 64, 128, 2, 16, 32, 2) == "nmajor"
         assert ops.conv3x3_staging(d, 8, 24, 3, 6, 10, 1) == "nmajor"
-    # the env-gated records keep the staging they were measured with
-    monkeypatch.setenv("OLSIM_CONV_V8", "1")
-    assert ops.conv3x3_staging("fwd", 64, 64, 1, 32, 32, 1) == "nmajor"
-    monkeypatch.delenv("OLSIM_CONV_V8")
+    # the env-gated record keeps the staging it was measured with
     monkeypatch.setenv("OLSIM_CONV_DW64", "1")
     assert ops.conv3x3_staging("dgrad", 64, 64, 1, 32, 32, 1) == "nmajor"
     monkeypatch.delenv("OLSIM_CONV_DW64")

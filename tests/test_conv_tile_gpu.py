@@ -13,9 +13,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
-CONV_VARS = ("OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
-             "OLSIM_CONV_DW8", "OLSIM_CONV_NMAJOR", "OLSIM_CONV_BM64",
-             "OLSIM_DGRAD_WT")
+CONV_VARS = ("OLSIM_CONV_V", "OLSIM_CONV_DW64", "OLSIM_CONV_DW8",
+             "OLSIM_CONV_NMAJOR", "OLSIM_CONV_BM64", "OLSIM_DGRAD_WT")
 TALL, WIDE = "128x64", "64x128"
 
 # (C, IC, OC, B, H, W, stride) -> the forward kernel it reaches
@@ -153,13 +152,10 @@ def test_shapes_that_keep_the_wide_tile(ops, monkeypatch):
         C, IC, OC, B, H, W, s = shape
         for d in ("dgrad", "wgrad"):
             assert ops.conv3x3_tile(d, IC, OC, B, H, W, s) == WIDE
-    # the env-gated records and the v5 family keep theirs
+    # the v5 family keeps its own
     probe = (2, 64, 128, 2, 8, 16, 1)
     if SHAPES[probe] not in GATED:
         assert _tile(ops, probe) == TALL
-    monkeypatch.setenv("OLSIM_CONV_V8", "1")
-    assert _tile(ops, probe) == WIDE
-    monkeypatch.delenv("OLSIM_CONV_V8")
     monkeypatch.setenv("OLSIM_CONV_V", "5")
     assert _tile(ops, probe) == WIDE
 

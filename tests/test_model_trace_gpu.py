@@ -17,9 +17,8 @@ pytestmark = pytest.mark.gpu
 ENVS = {"default": {}, "gn_pad0": {"OLSIM_GN_PAD": "0"},
         "dgrad_wt0": {"OLSIM_DGRAD_WT": "0"}}
 SWITCHES = ("OLSIM_GN_PAD", "OLSIM_DGRAD_WT", "OLSIM_CONV", "OLSIM_CONV_V",
-            "OLSIM_CONV_V8", "OLSIM_CONV_DW64", "OLSIM_CONV_DW8",
-            "OLSIM_CONV_NMAJOR", "OLSIM_CONV_BM64", "OLSIM_CONV5",
-            "OLSIM_PAD", "OLSIM_BMM_SAFE")
+            "OLSIM_CONV_DW64", "OLSIM_CONV_DW8", "OLSIM_CONV_NMAJOR",
+            "OLSIM_CONV_BM64", "OLSIM_CONV5", "OLSIM_PAD", "OLSIM_BMM_SAFE")
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -14,9 +14,8 @@ pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 # (C, OC, IC), as tests/test_conv_wflip_gpu.py
 CASES = [(1, 32, 32), (3, 64, 64), (2, 32, 96), (2, 96, 32), (2, 128, 64)]
-ENV_VARS = ("OLSIM_CONV", "OLSIM_CONV_V", "OLSIM_CONV_V8", "OLSIM_CONV_DW64",
-            "OLSIM_CONV_DW8", "OLSIM_CONV_NMAJOR", "OLSIM_DGRAD_WT",
-            "OLSIM_GN_PAD")
+ENV_VARS = ("OLSIM_CONV", "OLSIM_CONV_V", "OLSIM_CONV_DW64", "OLSIM_CONV_DW8",
+            "OLSIM_CONV_NMAJOR", "OLSIM_DGRAD_WT", "OLSIM_GN_PAD")
 
 
 @pytest.fixture(scope="module")
