@@ -7,6 +7,8 @@ dimension [C, ...], one `blinear` bmm (hipBLASLt -> MFMA on gfx950)
 processes all co-resident clients at once, and the input projection of
 the whole sequence is hoisted into a single large GEMM so the
 per-timestep recurrence only does the [C,B,H]x[C,H,4H] hidden GEMM.
+Where ops.lstm_route says "fused" the recurrence of a layer is one HIP
+kernel per direction; elsewhere it is the loop below.
 """
 
 from __future__ import annotations
@@ -15,6 +17,7 @@ from typing import Optional
 
 import torch
 
+from ..ops.lstm import lstm_layer, lstm_route
 from .base import ClientBatchedModel, Params, binit, blinear
 
 
@@ -75,6 +78,11 @@ class CharLSTM(ClientBatchedModel):
             # whole-sequence input projection: one big batched GEMM
             xp = blinear(hs.reshape(C, B * L, hs.shape[-1]), w_ih, bias) \
                 .view(C, B, L, 4 * h)
+            # bf16 on the GPU at B <= 16, H % 64 == 0, H <= 256: the whole
+            # recurrence in one kernel per direction (ops/csrc/lstm.hip)
+            if lstm_route(xp, w_hh) == "fused":
+                hs = lstm_layer(xp, w_hh)
+                continue
             ht = torch.zeros(C, B, h, device=x.device, dtype=hs.dtype)
             ct = torch.zeros_like(ht)
             outs = []

@@ -20,10 +20,11 @@ from .fused import (
     apply_aggregate,
     cross_entropy_fwd_bwd,
 )
+from .lstm import lstm_layer, lstm_route
 
 __all__ = [
     "hip_ops_available", "load_hip_ops", "fused_sgd_update",
     "weighted_delta_accum", "client_delta_sqnorm", "clip_weights",
     "weighted_delta_accum_quant", "uplink_uniform", "uplink_bytes_per_client",
-    "apply_aggregate", "cross_entropy_fwd_bwd",
+    "apply_aggregate", "cross_entropy_fwd_bwd", "lstm_layer", "lstm_route",
 ]

@@ -308,6 +308,85 @@ std::string server_opt_route(int64_t n, bool aligned) {
   return ols_server_opt_route(n, aligned);
 }
 
+// ---- fused LSTM recurrence (lstm.hip) --------------------------------------
+// xp [C, B, L, 4H] (input projection, bias included) and w_hh [C, H, 4H];
+// hs [C, B, L, H], gates [C, B, L, 4H] (post-nonlinearity, i|f|g|o) and
+// cs [C, B, L, H] fp32 are written.  The outputs are arguments so that a
+// caller decides where they live.  Everything but cs is bf16; every
+// operand is contiguous, on one GPU and on a 16-byte boundary, and the
+// shape is one lstm_route() calls "fused": anything else is an error here,
+// never a quiet detour.
+
+struct LstmDims {
+  int C, B, L, H;
+};
+
+LstmDims lstm_dims(const char* op, const at::Tensor& w,
+                   std::initializer_list<std::pair<const at::Tensor*, int>>
+                       acts,
+                   const at::Tensor& cs) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 3 && w.size(2) == 4 * w.size(1), op,
+              ": w_hh must be a [C, H, 4H] GPU tensor, got ", w.sizes());
+  const int64_t C = w.size(0), H = w.size(1);
+  const at::Tensor& first = *acts.begin()->first;
+  TORCH_CHECK(first.dim() == 4, op, ": activations must be 4-D");
+  const int64_t B = first.size(1), L = first.size(2);
+  auto check = [&](const at::Tensor& t, int mult, at::ScalarType dt) {
+    TORCH_CHECK(t.is_cuda() && t.device() == w.device() &&
+                    t.is_contiguous() && t.scalar_type() == dt &&
+                    reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                op, ": operands must be contiguous, 16-byte aligned, on "
+                "w_hh's GPU, bf16 (cs: fp32)");
+    TORCH_CHECK(t.sizes() == at::IntArrayRef({C, B, L, mult * H}), op,
+                ": operand is ", t.sizes(), ", expected ",
+                at::IntArrayRef({C, B, L, mult * H}));
+  };
+  TORCH_CHECK(w.is_contiguous() && w.scalar_type() == at::kBFloat16 &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              op, ": w_hh must be contiguous, 16-byte aligned bf16");
+  for (const auto& a : acts) check(*a.first, a.second, at::kBFloat16);
+  check(cs, 1, at::kFloat);
+  TORCH_CHECK(std::string(ols_lstm_route((int)B, (int)H, 1, 1)) == "fused",
+              op, ": B = ", B, ", H = ", H, " is not a fused shape (1 <= B "
+              "<= 16, H a multiple of 64 up to 256)");
+  TORCH_CHECK(C * B * L * 4 * H < (int64_t(1) << 40) && C < (1 << 24), op,
+              ": problem too large");
+  return {(int)C, (int)B, (int)L, (int)H};
+}
+
+void lstm_fwd(at::Tensor xp, at::Tensor w_hh, at::Tensor hs, at::Tensor gates,
+              at::Tensor cs) {
+  const LstmDims d =
+      lstm_dims("lstm_fwd", w_hh, {{&xp, 4}, {&hs, 1}, {&gates, 4}}, cs);
+  auto wpack = at::empty_like(w_hh);
+  const int rc = ols_lstm_fwd(xp.data_ptr(), w_hh.data_ptr(),
+                              wpack.data_ptr(), hs.data_ptr(),
+                              gates.data_ptr(), cs.data_ptr<float>(), d.C,
+                              d.B, d.L, d.H,
+                              at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "lstm_fwd: launcher refused the operands");
+}
+
+void lstm_bwd(at::Tensor dhs, at::Tensor gates, at::Tensor cs,
+              at::Tensor w_hh, at::Tensor dgates) {
+  const LstmDims d =
+      lstm_dims("lstm_bwd", w_hh, {{&dhs, 1}, {&gates, 4}, {&dgates, 4}}, cs);
+  const int rc = ols_lstm_bwd(dhs.data_ptr(), gates.data_ptr(),
+                              cs.data_ptr<float>(), w_hh.data_ptr(),
+                              dgates.data_ptr(), d.C, d.B, d.L, d.H,
+                              at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "lstm_bwd: launcher refused the operands");
+}
+
+// "fused" or "torch": the path a layer of batch B and hidden size H takes
+// (lstm_route.h), given its dtype and whether every operand is contiguous
+// and starts on a 16-byte boundary
+std::string lstm_route(int64_t B, int64_t H, bool is_bf16, bool aligned) {
+  TORCH_CHECK(B >= 0 && H >= 0 && B < (1 << 30) && H < (1 << 30),
+              "lstm_route: B, H out of range");
+  return ols_lstm_route((int)B, (int)H, is_bf16, aligned);
+}
+
 std::tuple<at::Tensor, at::Tensor> cross_entropy_fwd_bwd(at::Tensor logits,
                                                          at::Tensor labels) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous());
@@ -1030,6 +1109,12 @@ TORCH_LIBRARY(olsim_hip, m) {
         "Tensor(c!) v, Tensor? z, float total_weight, float sigma, float lr, "
         "float beta1, float beta2, float tau) -> ()");
   m.def("server_opt_route(int n, bool aligned) -> str", &server_opt_route);
+  m.def("lstm_fwd(Tensor xp, Tensor w_hh, Tensor(a!) hs, Tensor(b!) gates, "
+        "Tensor(c!) cs) -> ()");
+  m.def("lstm_bwd(Tensor dhs, Tensor gates, Tensor cs, Tensor w_hh, "
+        "Tensor(a!) dgates) -> ()");
+  m.def("lstm_route(int B, int H, bool is_bf16, bool aligned) -> str",
+        &lstm_route);
   m.def("cross_entropy_fwd_bwd(Tensor logits, Tensor labels) -> (Tensor, Tensor)");
   m.def("groupnorm_fwd(Tensor x, Tensor res, Tensor gamma, Tensor beta, "
         "int clients, int groups, float eps, bool relu) -> (Tensor, Tensor, Tensor)");
@@ -1087,6 +1172,8 @@ TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("clip_weights", &clip_weights);
   m.impl("delta_accum_quant", &delta_accum_quant);
   m.impl("server_opt_step", &server_opt_step);
+  m.impl("lstm_fwd", &lstm_fwd);
+  m.impl("lstm_bwd", &lstm_bwd);
   m.impl("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.impl("groupnorm_fwd", &groupnorm_fwd);
   m.impl("groupnorm_bwd", &groupnorm_bwd);

@@ -72,6 +72,22 @@ extern "C" void ols_server_opt_step(int kind, float* x, const float* d,
 // whether every operand starts on a 16-byte boundary
 extern "C" const char* ols_server_opt_route(int64_t n, int aligned);
 
+// lstm.hip: one LSTM layer's recurrence, one workgroup per client.
+// xp [C,B,L,4H] and w [C,H,4H] bf16; hs [C,B,L,H] and gates [C,B,L,4H]
+// bf16, cs [C,B,L,H] fp32; wpack: C*H*4H bf16 of scratch for the
+// fragment-major weights.  Both return 1 and launch nothing where
+// lstm_route.h says "torch" (B, H, or a pointer off a 16-byte boundary).
+extern "C" int ols_lstm_fwd(const void* xp, const void* w, void* wpack,
+                            void* hs, void* gates, float* cs, int C, int B,
+                            int L, int H, hipStream_t stream);
+// dgates [C,B,L,4H] bf16 from dhs [C,B,L,H] and what the forward saved
+extern "C" int ols_lstm_bwd(const void* dhs, const void* gates,
+                            const float* cs, const void* w, void* dgates,
+                            int C, int B, int L, int H, hipStream_t stream);
+// "fused" or "torch" (lstm_route.h)
+extern "C" const char* ols_lstm_route(int B, int H, int is_bf16,
+                                      int aligned);
+
 extern "C" void ols_cross_entropy_fwd_bwd(
     const void* logits, const int64_t* labels, float* loss, void* dlogits,
     int64_t nrows, int64_t K, float inv_n, int dtype, hipStream_t stream);
