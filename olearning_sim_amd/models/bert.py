@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from .base import (ClientBatchedModel, Params, binit, blinear, blayernorm)
+from ..ops.attn import attn_route, causal_attention
 
 
 class _TiedHeadCE(torch.autograd.Function):
@@ -172,13 +173,19 @@ class BertLM(ClientBatchedModel):
             pre = f"l{i}"
             qkv = blinear(hs.view(C, B * L, h), params[f"{pre}.qkv.w"],
                           params[f"{pre}.qkv.b"])          # [C, B*L, 3H]
-            qkv = qkv.view(C * B, L, 3, nh, hd).permute(2, 0, 3, 1, 4)
-            # strided q/k/v slices: verified correct and ~20% faster
-            # than materialised copies on this stack (tools/
-            # sdpaprobe.py, maxerr 0.0 incl. backward at C*B=500)
-            q, k, v = qkv[0], qkv[1], qkv[2]               # [C*B, nh, L, hd]
-            att = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-            att = att.transpose(1, 2).reshape(C, B * L, h)
+            qkv = qkv.view(C, B, L, 3 * h)
+            if attn_route(qkv, nh) == "fused":
+                # ops/csrc/attn.hip reads the packed qkv and writes the
+                # layout attn_out reads: no permute, no transpose copy
+                att = causal_attention(qkv, nh).view(C, B * L, h)
+            else:
+                qkv = qkv.view(C * B, L, 3, nh, hd).permute(2, 0, 3, 1, 4)
+                # strided q/k/v slices: verified correct and ~20% faster
+                # than materialised copies on this stack (tools/
+                # sdpaprobe.py, maxerr 0.0 incl. backward at C*B=500)
+                q, k, v = qkv[0], qkv[1], qkv[2]           # [C*B, nh, L, hd]
+                att = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+                att = att.transpose(1, 2).reshape(C, B * L, h)
             hs = hs + blinear(att, params[f"{pre}.attn_out.w"],
                               params[f"{pre}.attn_out.b"]).view(C, B, L, h)
             hs = blayernorm(hs, params[f"{pre}.ln1.g"], params[f"{pre}.ln1.b"])

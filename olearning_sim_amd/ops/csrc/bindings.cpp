@@ -387,6 +387,79 @@ std::string lstm_route(int64_t B, int64_t H, bool is_bf16, bool aligned) {
   return ols_lstm_route((int)B, (int)H, is_bf16, aligned);
 }
 
+// ---- fused causal self-attention (attn.hip) --------------------------------
+// qkv [C, B, L, 3H] as the qkv blinear packs it (q | k | v along 3H, each
+// heads x HD), att and datt [C, B, L, H], lse [C*B, heads, L] fp32, dqkv
+// like qkv.  The outputs are arguments so that a caller decides where they
+// live.  Every operand is contiguous, on one GPU and on a 16-byte
+// boundary, bf16 but for lse, and the shape is one attn_route() calls
+// "fused": anything else is an error here, never a quiet detour.
+
+struct AttnDims {
+  int CB, L, heads, HD;
+};
+
+AttnDims attn_dims(const char* op, const at::Tensor& qkv, int64_t heads,
+                   std::initializer_list<const at::Tensor*> like_qkv,
+                   std::initializer_list<const at::Tensor*> like_att,
+                   const at::Tensor& lse) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 4 && heads >= 1 &&
+                  qkv.size(3) % (3 * heads) == 0,
+              op, ": qkv must be a [C, B, L, 3*heads*HD] GPU tensor, got ",
+              qkv.sizes(), " for ", heads, " heads");
+  const int64_t C = qkv.size(0), B = qkv.size(1), L = qkv.size(2);
+  const int64_t H = qkv.size(3) / 3, HD = H / heads;
+  auto check = [&](const at::Tensor& t, at::ScalarType dt,
+                   at::IntArrayRef shape) {
+    TORCH_CHECK(t.is_cuda() && t.device() == qkv.device() &&
+                    t.is_contiguous() && t.scalar_type() == dt &&
+                    reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                op, ": operands must be contiguous, 16-byte aligned, on "
+                "qkv's GPU, bf16 (lse: fp32)");
+    TORCH_CHECK(t.sizes() == shape, op, ": operand is ", t.sizes(),
+                ", expected ", shape);
+  };
+  for (const at::Tensor* t : like_qkv) check(*t, at::kBFloat16, {C, B, L, 3 * H});
+  for (const at::Tensor* t : like_att) check(*t, at::kBFloat16, {C, B, L, H});
+  check(lse, at::kFloat, {C * B, heads, L});
+  TORCH_CHECK(L < (1 << 30) && HD < (1 << 30) &&
+                  std::string(ols_attn_route((int)L, (int)HD, 1, 1)) == "fused",
+              op, ": L = ", L, ", HD = ", HD, " is not a fused shape (1 <= L "
+              "<= 128, HD 32 or 64)");
+  TORCH_CHECK(C * B * heads < (int64_t(1) << 31) &&
+                  C * B * L * 3 * H < (int64_t(1) << 40),
+              op, ": problem too large");
+  return {(int)(C * B), (int)L, (int)heads, (int)HD};
+}
+
+void attn_fwd(at::Tensor qkv, at::Tensor att, at::Tensor lse, int64_t heads) {
+  const AttnDims d = attn_dims("attn_fwd", qkv, heads, {&qkv}, {&att}, lse);
+  const int rc = ols_attn_fwd(qkv.data_ptr(), att.data_ptr(),
+                              lse.data_ptr<float>(), d.CB, d.L, d.heads, d.HD,
+                              at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "attn_fwd: launcher refused the operands");
+}
+
+void attn_bwd(at::Tensor qkv, at::Tensor att, at::Tensor datt, at::Tensor lse,
+              at::Tensor dqkv, int64_t heads) {
+  const AttnDims d =
+      attn_dims("attn_bwd", qkv, heads, {&qkv, &dqkv}, {&att, &datt}, lse);
+  const int rc = ols_attn_bwd(qkv.data_ptr(), att.data_ptr(), datt.data_ptr(),
+                              lse.data_ptr<float>(), dqkv.data_ptr(), d.CB,
+                              d.L, d.heads, d.HD,
+                              at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "attn_bwd: launcher refused the operands");
+}
+
+// "fused" or "torch": the path a layer of sequence length L and head size
+// HD takes (attn_route.h), given its dtype and whether every operand is
+// contiguous and starts on a 16-byte boundary
+std::string attn_route(int64_t L, int64_t HD, bool is_bf16, bool aligned) {
+  TORCH_CHECK(L >= 0 && HD >= 0 && L < (1 << 30) && HD < (1 << 30),
+              "attn_route: L, HD out of range");
+  return ols_attn_route((int)L, (int)HD, is_bf16, aligned);
+}
+
 std::tuple<at::Tensor, at::Tensor> cross_entropy_fwd_bwd(at::Tensor logits,
                                                          at::Tensor labels) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous());
@@ -1115,6 +1188,11 @@ TORCH_LIBRARY(olsim_hip, m) {
         "Tensor(a!) dgates) -> ()");
   m.def("lstm_route(int B, int H, bool is_bf16, bool aligned) -> str",
         &lstm_route);
+  m.def("attn_fwd(Tensor qkv, Tensor(a!) att, Tensor(b!) lse, int heads) -> ()");
+  m.def("attn_bwd(Tensor qkv, Tensor att, Tensor datt, Tensor lse, "
+        "Tensor(a!) dqkv, int heads) -> ()");
+  m.def("attn_route(int L, int HD, bool is_bf16, bool aligned) -> str",
+        &attn_route);
   m.def("cross_entropy_fwd_bwd(Tensor logits, Tensor labels) -> (Tensor, Tensor)");
   m.def("groupnorm_fwd(Tensor x, Tensor res, Tensor gamma, Tensor beta, "
         "int clients, int groups, float eps, bool relu) -> (Tensor, Tensor, Tensor)");
@@ -1174,6 +1252,8 @@ TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("server_opt_step", &server_opt_step);
   m.impl("lstm_fwd", &lstm_fwd);
   m.impl("lstm_bwd", &lstm_bwd);
+  m.impl("attn_fwd", &attn_fwd);
+  m.impl("attn_bwd", &attn_bwd);
   m.impl("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.impl("groupnorm_fwd", &groupnorm_fwd);
   m.impl("groupnorm_bwd", &groupnorm_bwd);

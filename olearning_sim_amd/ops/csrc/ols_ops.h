@@ -88,6 +88,22 @@ extern "C" int ols_lstm_bwd(const void* dhs, const void* gates,
 extern "C" const char* ols_lstm_route(int B, int H, int is_bf16,
                                       int aligned);
 
+// attn.hip: causal self-attention of one layer, one workgroup per (client x
+// batch row, head).  qkv [CB, L, 3, heads, HD] and att [CB, L, heads*HD]
+// bf16, lse [CB, heads, L] fp32.  Both return 1 and launch nothing where
+// attn_route.h says "torch" (L, HD, or a pointer off a 16-byte boundary).
+extern "C" int ols_attn_fwd(const void* qkv, void* att, float* lse, int CB,
+                            int L, int heads, int HD, hipStream_t stream);
+// dqkv, packed like qkv and written whole, from datt [CB, L, heads*HD] and
+// what the forward read and wrote
+extern "C" int ols_attn_bwd(const void* qkv, const void* att,
+                            const void* datt, const float* lse, void* dqkv,
+                            int CB, int L, int heads, int HD,
+                            hipStream_t stream);
+// "fused" or "torch" (attn_route.h)
+extern "C" const char* ols_attn_route(int L, int HD, int is_bf16,
+                                      int aligned);
+
 extern "C" void ols_cross_entropy_fwd_bwd(
     const void* logits, const int64_t* labels, float* loss, void* dlogits,
     int64_t nrows, int64_t K, float inv_n, int dtype, hipStream_t stream);
