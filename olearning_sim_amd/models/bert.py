@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from .base import (ClientBatchedModel, Params, binit, blinear, blayernorm)
 from ..ops.attn import attn_route, causal_attention
+from ..ops.head_ce import head_ce_grad, head_ce_route, head_ce_stats
 
 
 class _TiedHeadCE(torch.autograd.Function):
@@ -28,7 +29,9 @@ class _TiedHeadCE(torch.autograd.Function):
     backward (docs/ROUND2_DESIGN.md §5).  All GEMMs are client-batched
     bmm on natural-layout operands (the hipBLASLt strided-transpose
     fault, models/base.py, is avoided by materialising per-slice
-    transposes of the SMALL dlogits tile only)."""
+    transposes of the SMALL dlogits tile only).  Between the GEMMs a bf16
+    GPU tile goes through one kernel per slice and direction
+    (ops/head_ce.py); every other tile keeps the eager body."""
 
     SLICE_V = 8192
 
@@ -49,10 +52,15 @@ class _TiedHeadCE(torch.autograd.Function):
                        dtype=torch.float32)
         l = torch.zeros(C, N, device=hs.device, dtype=torch.float32)
         zy = torch.zeros(C, N, device=hs.device, dtype=torch.float32)
-        lab = labels.view(C, N)
+        lab = labels.view(C, N).contiguous()
         for s0 in range(0, V, sv):
             s1 = min(s0 + sv, V)
-            logits = torch.bmm(hs, tok_t[:, :, s0:s1]).float() \
+            tile = torch.bmm(hs, tok_t[:, :, s0:s1])
+            if head_ce_route(tile, bias) != "torch":
+                # ops/csrc/head_ce.hip: one pass over the bf16 tile
+                head_ce_stats(tile, bias, lab, s0, m, l, zy)
+                continue
+            logits = tile.float() \
                 + bias[:, s0:s1].float().unsqueeze(1)
             m_new = torch.maximum(m, logits.max(dim=2).values)
             l = l * torch.exp(m - m_new) + \
@@ -80,16 +88,22 @@ class _TiedHeadCE(torch.autograd.Function):
         flat_rows = torch.arange(C * N, device=hs.device)
         for s0 in range(0, V, sv):
             s1 = min(s0 + sv, V)
-            logits = torch.bmm(hs, tok_t[:, :, s0:s1]).float() \
-                + bias[:, s0:s1].float().unsqueeze(1)
-            p = torch.exp(logits - lse)                  # softmax slice
-            sel = (lab >= s0) & (lab < s1)
-            idx = (lab - s0).clamp(0, s1 - s0 - 1)
-            pf = p.view(C * N, s1 - s0)
-            self_ = sel.view(-1)
-            pf[flat_rows[self_], idx.view(-1)[self_]] -= 1.0
-            dlogits = (p * g).to(hs.dtype)               # [C, N, s]
-            dbias[:, s0:s1] = dlogits.sum(dim=1).to(bias.dtype)
+            tile = torch.bmm(hs, tok_t[:, :, s0:s1])
+            if head_ce_route(tile, bias) != "torch":
+                # dlogits over the tile it was computed from, dbias slice
+                dlogits = head_ce_grad(tile, bias, lab, s0, m, l, g, dbias,
+                                       out=tile)
+            else:
+                logits = tile.float() \
+                    + bias[:, s0:s1].float().unsqueeze(1)
+                p = torch.exp(logits - lse)              # softmax slice
+                sel = (lab >= s0) & (lab < s1)
+                idx = (lab - s0).clamp(0, s1 - s0 - 1)
+                pf = p.view(C * N, s1 - s0)
+                self_ = sel.view(-1)
+                pf[flat_rows[self_], idx.view(-1)[self_]] -= 1.0
+                dlogits = (p * g).to(hs.dtype)           # [C, N, s]
+                dbias[:, s0:s1] = dlogits.sum(dim=1).to(bias.dtype)
             # tok slice is non-transposed (safe); dlogits' transpose is
             # of a fresh contiguous tensor (full-tensor view, safe)
             dhs += torch.bmm(dlogits, tok[:, s0:s1].to(hs.dtype))

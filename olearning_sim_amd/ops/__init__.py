@@ -22,11 +22,13 @@ from .fused import (
 )
 from .lstm import lstm_layer, lstm_route
 from .attn import attn_route, causal_attention
+from .head_ce import head_ce_grad, head_ce_route, head_ce_stats
 
 __all__ = [
     "hip_ops_available", "load_hip_ops", "fused_sgd_update",
     "weighted_delta_accum", "client_delta_sqnorm", "clip_weights",
     "weighted_delta_accum_quant", "uplink_uniform", "uplink_bytes_per_client",
     "apply_aggregate", "cross_entropy_fwd_bwd", "lstm_layer", "lstm_route",
-    "causal_attention", "attn_route",
+    "causal_attention", "attn_route", "head_ce_route", "head_ce_stats",
+    "head_ce_grad",
 ]

@@ -460,6 +460,115 @@ std::string attn_route(int64_t L, int64_t HD, bool is_bf16, bool aligned) {
   return ols_attn_route((int)L, (int)HD, is_bf16, aligned);
 }
 
+// ---- tied-head cross-entropy between the GEMMs (head_ce.hip) ---------------
+// One vocab slice [s0, s0 + s): logits [C, N, s] as the bmm wrote it, bias
+// [C, V] with unit column stride and any client stride (0 for an expanded
+// 1-D bias), labels [C, N] int64, the per-row state m, l, zy [C, N] fp32.
+// The tile is bf16, contiguous and on a 16-byte boundary, everything is on
+// one GPU, and the slice lies inside V: anything else is an error here,
+// never a quiet detour.
+
+struct HeadCeDims {
+  int C, N, s;
+  int64_t V, bias_stride;
+};
+
+HeadCeDims head_ce_dims(const char* op, const at::Tensor& logits,
+                        const at::Tensor& bias, const at::Tensor& labels,
+                        int64_t s0,
+                        std::initializer_list<const at::Tensor*> state) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 3 &&
+                  logits.scalar_type() == at::kBFloat16 &&
+                  logits.is_contiguous(),
+              op, ": logits must be a contiguous bf16 [C, N, s] GPU tensor, "
+              "got ", logits.sizes());
+  const int64_t C = logits.size(0), N = logits.size(1), s = logits.size(2);
+  TORCH_CHECK(C >= 1 && C <= 65535 && N >= 1 && N < (int64_t(1) << 31) &&
+                  s >= 1 && s < (int64_t(1) << 30),
+              op, ": C = ", C, ", N = ", N, ", s = ", s, " out of range");
+  const bool aligned =
+      reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0;
+  TORCH_CHECK(std::string(ols_head_ce_route(s, 1, aligned)) != "torch", op,
+              ": logits must start on a 16-byte boundary");
+  TORCH_CHECK(bias.is_cuda() && bias.device() == logits.device() &&
+                  bias.dim() == 2 && bias.size(0) == C &&
+                  bias.scalar_type() == at::kBFloat16 &&
+                  (bias.size(1) == 1 || bias.stride(1) == 1) &&
+                  bias.stride(0) >= 0,
+              op, ": bias must be a bf16 [C, V] tensor on the logits' GPU "
+              "with unit column stride, got ", bias.sizes());
+  const int64_t V = bias.size(1);
+  TORCH_CHECK(s0 >= 0 && s0 + s <= V, op, ": slice [", s0, ", ", s0 + s,
+              ") is outside V = ", V);
+  auto rows = [&](const at::Tensor& t, at::ScalarType dt, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.device() == logits.device() &&
+                    t.is_contiguous() && t.scalar_type() == dt &&
+                    t.sizes() == at::IntArrayRef({C, N}),
+                op, ": ", what, " must be contiguous [C, N] on the logits' "
+                "GPU (labels int64, m, l, zy fp32), got ", t.sizes());
+  };
+  rows(labels, at::kLong, "labels");
+  for (const at::Tensor* t : state) rows(*t, at::kFloat, "m, l, zy");
+  return {(int)C, (int)N, (int)s, V, bias.stride(0)};
+}
+
+// m, l, zy <- the online-softmax merge of this slice into them
+void head_ce_stats(at::Tensor logits, at::Tensor bias, at::Tensor labels,
+                   int64_t s0, at::Tensor m, at::Tensor l, at::Tensor zy) {
+  const HeadCeDims d =
+      head_ce_dims("head_ce_stats", logits, bias, labels, s0, {&m, &l, &zy});
+  const int rc = ols_head_ce_stats(
+      logits.data_ptr(), bias.data_ptr(), d.bias_stride,
+      labels.data_ptr<int64_t>(), m.data_ptr<float>(), l.data_ptr<float>(),
+      zy.data_ptr<float>(), d.C, d.N, d.s, s0,
+      at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "head_ce_stats: launcher refused the operands");
+}
+
+// out <- bf16(g * (exp(z - m - log l) - onehot)), dbias[:, s0 : s0 + s] <-
+// its column sums.  out MAY BE logits ITSELF: every thread reads its own
+// elements before it writes them.  Any other overlap of the two is refused.
+void head_ce_grad(at::Tensor logits, at::Tensor bias, at::Tensor labels,
+                  int64_t s0, at::Tensor m, at::Tensor l, at::Tensor g,
+                  at::Tensor dbias, at::Tensor out) {
+  const HeadCeDims d =
+      head_ce_dims("head_ce_grad", logits, bias, labels, s0, {&m, &l});
+  TORCH_CHECK(out.is_cuda() && out.device() == logits.device() &&
+                  out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+                  out.sizes() == logits.sizes() &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "head_ce_grad: out must be like logits: contiguous bf16 on a "
+              "16-byte boundary");
+  const char* lo = static_cast<const char*>(logits.data_ptr());
+  const char* oo = static_cast<const char*>(out.data_ptr());
+  const int64_t nbytes = logits.numel() * 2;
+  TORCH_CHECK(oo == lo || oo + nbytes <= lo || lo + nbytes <= oo,
+              "head_ce_grad: out must be logits itself or not overlap it");
+  TORCH_CHECK(g.is_cuda() && g.device() == logits.device() &&
+                  g.scalar_type() == at::kFloat && g.numel() == 1,
+              "head_ce_grad: g must be one fp32 element on the logits' GPU");
+  TORCH_CHECK(dbias.is_cuda() && dbias.device() == logits.device() &&
+                  dbias.scalar_type() == at::kBFloat16 &&
+                  dbias.is_contiguous() &&
+                  dbias.sizes() == at::IntArrayRef({d.C, d.V}),
+              "head_ce_grad: dbias must be contiguous bf16 [C, V], got ",
+              dbias.sizes());
+  const int rc = ols_head_ce_grad(
+      logits.data_ptr(), out.data_ptr(), bias.data_ptr(), d.bias_stride,
+      labels.data_ptr<int64_t>(), m.data_ptr<float>(), l.data_ptr<float>(),
+      g.data_ptr<float>(), dbias.data_ptr(), d.V, d.C, d.N, d.s, s0,
+      at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "head_ce_grad: launcher refused the operands");
+}
+
+// "fused8", "fused2", "fused1" or "torch": the path a slice of s columns
+// takes (head_ce_route.h), given the tile's dtype and whether it is
+// contiguous and starts on a 16-byte boundary
+std::string head_ce_route(int64_t s, bool is_bf16, bool aligned) {
+  TORCH_CHECK(s >= 0, "head_ce_route: s >= 0");
+  return ols_head_ce_route(s, is_bf16, aligned);
+}
+
 std::tuple<at::Tensor, at::Tensor> cross_entropy_fwd_bwd(at::Tensor logits,
                                                          at::Tensor labels) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous());
@@ -1193,6 +1302,13 @@ TORCH_LIBRARY(olsim_hip, m) {
         "Tensor(a!) dqkv, int heads) -> ()");
   m.def("attn_route(int L, int HD, bool is_bf16, bool aligned) -> str",
         &attn_route);
+  m.def("head_ce_stats(Tensor logits, Tensor bias, Tensor labels, int s0, "
+        "Tensor(a!) m, Tensor(b!) l, Tensor(c!) zy) -> ()");
+  m.def("head_ce_grad(Tensor logits, Tensor bias, Tensor labels, int s0, "
+        "Tensor m, Tensor l, Tensor g, Tensor(a!) dbias, Tensor(b!) out) "
+        "-> ()");
+  m.def("head_ce_route(int s, bool is_bf16, bool aligned) -> str",
+        &head_ce_route);
   m.def("cross_entropy_fwd_bwd(Tensor logits, Tensor labels) -> (Tensor, Tensor)");
   m.def("groupnorm_fwd(Tensor x, Tensor res, Tensor gamma, Tensor beta, "
         "int clients, int groups, float eps, bool relu) -> (Tensor, Tensor, Tensor)");
@@ -1254,6 +1370,8 @@ TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("lstm_bwd", &lstm_bwd);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
+  m.impl("head_ce_stats", &head_ce_stats);
+  m.impl("head_ce_grad", &head_ce_grad);
   m.impl("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.impl("groupnorm_fwd", &groupnorm_fwd);
   m.impl("groupnorm_bwd", &groupnorm_bwd);

@@ -104,6 +104,27 @@ extern "C" int ols_attn_bwd(const void* qkv, const void* att,
 extern "C" const char* ols_attn_route(int L, int HD, int is_bf16,
                                       int aligned);
 
+// head_ce.hip: one vocab slice [s0, s0 + s) of the tied head's cross-entropy.
+// logits [C, N, s] bf16, bias strip at bias + c * bias_stride + s0 (stride 0:
+// one bias for all clients), labels [C, N], m, l, zy [C, N] fp32 updated in
+// place.  Both return 1 and launch nothing where head_ce_route.h says "torch"
+// (a tile off a 16-byte boundary) or a size is out of range.
+extern "C" int ols_head_ce_stats(const void* logits, const void* bias,
+                                 int64_t bias_stride, const int64_t* labels,
+                                 float* m, float* l, float* zy, int C, int N,
+                                 int s, int64_t s0, hipStream_t stream);
+// out [C, N, s] bf16 = g[0] * (softmax - onehot), out == logits allowed;
+// dbias [C, V] bf16, columns [s0, s0 + s) written
+extern "C" int ols_head_ce_grad(const void* logits, void* out,
+                                const void* bias, int64_t bias_stride,
+                                const int64_t* labels, const float* m,
+                                const float* l, const float* g, void* dbias,
+                                int64_t V, int C, int N, int s, int64_t s0,
+                                hipStream_t stream);
+// "fused8", "fused2", "fused1" or "torch" (head_ce_route.h)
+extern "C" const char* ols_head_ce_route(int64_t s, int is_bf16,
+                                         int aligned);
+
 extern "C" void ols_cross_entropy_fwd_bwd(
     const void* logits, const int64_t* labels, float* loss, void* dlogits,
     int64_t nrows, int64_t K, float inv_n, int dtype, hipStream_t stream);
