@@ -16,7 +16,8 @@ import torch
 import torch.nn.functional as F
 
 from .base import (ClientBatchedModel, Params, binit, blinear, blayernorm)
-from ..ops.attn import attn_route, causal_attention
+from ..ops.attn import (attn_long_route, attn_route, causal_attention,
+                        causal_attention_long)
 from ..ops.head_ce import head_ce_grad, head_ce_route, head_ce_stats
 
 
@@ -192,6 +193,9 @@ class BertLM(ClientBatchedModel):
                 # ops/csrc/attn.hip reads the packed qkv and writes the
                 # layout attn_out reads: no permute, no transpose copy
                 att = causal_attention(qkv, nh).view(C, B * L, h)
+            elif attn_long_route(qkv, nh) == "long":
+                # 129 <= L <= 512: ops/csrc/attn_long.hip, same layouts
+                att = causal_attention_long(qkv, nh).view(C, B * L, h)
             else:
                 qkv = qkv.view(C * B, L, 3, nh, hd).permute(2, 0, 3, 1, 4)
                 # strided q/k/v slices: verified correct and ~20% faster

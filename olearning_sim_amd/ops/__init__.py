@@ -21,7 +21,8 @@ from .fused import (
     cross_entropy_fwd_bwd,
 )
 from .lstm import lstm_layer, lstm_route
-from .attn import attn_route, causal_attention
+from .attn import (attn_long_route, attn_route, causal_attention,
+                   causal_attention_long)
 from .head_ce import head_ce_grad, head_ce_route, head_ce_stats
 
 __all__ = [
@@ -29,6 +30,7 @@ __all__ = [
     "weighted_delta_accum", "client_delta_sqnorm", "clip_weights",
     "weighted_delta_accum_quant", "uplink_uniform", "uplink_bytes_per_client",
     "apply_aggregate", "cross_entropy_fwd_bwd", "lstm_layer", "lstm_route",
-    "causal_attention", "attn_route", "head_ce_route", "head_ce_stats",
+    "causal_attention", "attn_route", "causal_attention_long",
+    "attn_long_route", "head_ce_route", "head_ce_stats",
     "head_ce_grad",
 ]

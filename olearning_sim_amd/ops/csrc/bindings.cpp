@@ -402,7 +402,7 @@ struct AttnDims {
 AttnDims attn_dims(const char* op, const at::Tensor& qkv, int64_t heads,
                    std::initializer_list<const at::Tensor*> like_qkv,
                    std::initializer_list<const at::Tensor*> like_att,
-                   const at::Tensor& lse) {
+                   const at::Tensor& lse, bool long_seq = false) {
   TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 4 && heads >= 1 &&
                   qkv.size(3) % (3 * heads) == 0,
               op, ": qkv must be a [C, B, L, 3*heads*HD] GPU tensor, got ",
@@ -422,10 +422,17 @@ AttnDims attn_dims(const char* op, const at::Tensor& qkv, int64_t heads,
   for (const at::Tensor* t : like_qkv) check(*t, at::kBFloat16, {C, B, L, 3 * H});
   for (const at::Tensor* t : like_att) check(*t, at::kBFloat16, {C, B, L, H});
   check(lse, at::kFloat, {C * B, heads, L});
-  TORCH_CHECK(L < (1 << 30) && HD < (1 << 30) &&
-                  std::string(ols_attn_route((int)L, (int)HD, 1, 1)) == "fused",
-              op, ": L = ", L, ", HD = ", HD, " is not a fused shape (1 <= L "
-              "<= 128, HD 32 or 64)");
+  TORCH_CHECK(L < (1 << 30) && HD < (1 << 30), op, ": L, HD out of range");
+  if (long_seq) {
+    TORCH_CHECK(std::string(ols_attn_long_route((int)L, (int)HD, 1, 1)) ==
+                    "long",
+                op, ": L = ", L, ", HD = ", HD, " is not a long shape (129 <= "
+                "L <= 512, HD 32 or 64)");
+  } else {
+    TORCH_CHECK(std::string(ols_attn_route((int)L, (int)HD, 1, 1)) == "fused",
+                op, ": L = ", L, ", HD = ", HD, " is not a fused shape (1 <= "
+                "L <= 128, HD 32 or 64)");
+  }
   TORCH_CHECK(C * B * heads < (int64_t(1) << 31) &&
                   C * B * L * 3 * H < (int64_t(1) << 40),
               op, ": problem too large");
@@ -458,6 +465,41 @@ std::string attn_route(int64_t L, int64_t HD, bool is_bf16, bool aligned) {
   TORCH_CHECK(L >= 0 && HD >= 0 && L < (1 << 30) && HD < (1 << 30),
               "attn_route: L, HD out of range");
   return ols_attn_route((int)L, (int)HD, is_bf16, aligned);
+}
+
+// ---- the same for 129 <= L <= 512 (attn_long.hip) --------------------------
+// Operands and checks as above; dsum [C*B, heads, L] fp32, shaped like lse,
+// is the backward's scratch for dO_i . O_i.
+
+void attn_long_fwd(at::Tensor qkv, at::Tensor att, at::Tensor lse,
+                   int64_t heads) {
+  const AttnDims d =
+      attn_dims("attn_long_fwd", qkv, heads, {&qkv}, {&att}, lse, true);
+  const int rc = ols_attn_long_fwd(qkv.data_ptr(), att.data_ptr(),
+                                   lse.data_ptr<float>(), d.CB, d.L, d.heads,
+                                   d.HD,
+                                   at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "attn_long_fwd: launcher refused the operands");
+}
+
+void attn_long_bwd(at::Tensor qkv, at::Tensor att, at::Tensor datt,
+                   at::Tensor lse, at::Tensor dsum, at::Tensor dqkv,
+                   int64_t heads) {
+  const AttnDims d = attn_dims("attn_long_bwd", qkv, heads, {&qkv, &dqkv},
+                               {&att, &datt}, lse, true);
+  attn_dims("attn_long_bwd", qkv, heads, {}, {}, dsum, true);
+  const int rc = ols_attn_long_bwd(
+      qkv.data_ptr(), att.data_ptr(), datt.data_ptr(), lse.data_ptr<float>(),
+      dsum.data_ptr<float>(), dqkv.data_ptr(), d.CB, d.L, d.heads, d.HD,
+      at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "attn_long_bwd: launcher refused the operands");
+}
+
+std::string attn_long_route(int64_t L, int64_t HD, bool is_bf16,
+                            bool aligned) {
+  TORCH_CHECK(L >= 0 && HD >= 0 && L < (1 << 30) && HD < (1 << 30),
+              "attn_long_route: L, HD out of range");
+  return ols_attn_long_route((int)L, (int)HD, is_bf16, aligned);
 }
 
 // ---- tied-head cross-entropy between the GEMMs (head_ce.hip) ---------------
@@ -1302,6 +1344,12 @@ TORCH_LIBRARY(olsim_hip, m) {
         "Tensor(a!) dqkv, int heads) -> ()");
   m.def("attn_route(int L, int HD, bool is_bf16, bool aligned) -> str",
         &attn_route);
+  m.def("attn_long_fwd(Tensor qkv, Tensor(a!) att, Tensor(b!) lse, int heads) "
+        "-> ()");
+  m.def("attn_long_bwd(Tensor qkv, Tensor att, Tensor datt, Tensor lse, "
+        "Tensor(a!) dsum, Tensor(b!) dqkv, int heads) -> ()");
+  m.def("attn_long_route(int L, int HD, bool is_bf16, bool aligned) -> str",
+        &attn_long_route);
   m.def("head_ce_stats(Tensor logits, Tensor bias, Tensor labels, int s0, "
         "Tensor(a!) m, Tensor(b!) l, Tensor(c!) zy) -> ()");
   m.def("head_ce_grad(Tensor logits, Tensor bias, Tensor labels, int s0, "
@@ -1370,6 +1418,8 @@ TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("lstm_bwd", &lstm_bwd);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
+  m.impl("attn_long_fwd", &attn_long_fwd);
+  m.impl("attn_long_bwd", &attn_long_bwd);
   m.impl("head_ce_stats", &head_ce_stats);
   m.impl("head_ce_grad", &head_ce_grad);
   m.impl("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);

@@ -104,6 +104,22 @@ extern "C" int ols_attn_bwd(const void* qkv, const void* att,
 extern "C" const char* ols_attn_route(int L, int HD, int is_bf16,
                                       int aligned);
 
+// attn_long.hip: the same operation for 129 <= L <= 512, one workgroup per
+// (client x batch row, head, block of 128 rows).  Operands as above; dsum
+// [CB, heads, L] fp32 is scratch the backward fills with dO_i . O_i before
+// its main kernel reads it.  Both return 1 and launch nothing where
+// attn_long_route() in attn_route.h says "torch".
+extern "C" int ols_attn_long_fwd(const void* qkv, void* att, float* lse,
+                                 int CB, int L, int heads, int HD,
+                                 hipStream_t stream);
+extern "C" int ols_attn_long_bwd(const void* qkv, const void* att,
+                                 const void* datt, const float* lse,
+                                 float* dsum, void* dqkv, int CB, int L,
+                                 int heads, int HD, hipStream_t stream);
+// "long" or "torch" (attn_route.h)
+extern "C" const char* ols_attn_long_route(int L, int HD, int is_bf16,
+                                           int aligned);
+
 // head_ce.hip: one vocab slice [s0, s0 + s) of the tied head's cross-entropy.
 // logits [C, N, s] bf16, bias strip at bias + c * bias_stride + s0 (stride 0:
 // one bias for all clients), labels [C, N], m, l, zy [C, N] fp32 updated in

@@ -9,7 +9,11 @@ Prints one JSON line: ms per route as the median over the repeats with
 their min..max spread, the kernel launches of one step (counted by the
 profiler), and the fused kernels' useful bytes/s and FLOP/s from the shapes.
 
-    python tools/attnbench.py [--clients 125] [--repeats 5]
+--seq-len L (default 128) times another length at the same 512 tokens per
+client (B = 512 // L): from 129 on the "fused" side is the long-sequence
+kernels of attn_long.hip.
+
+    python tools/attnbench.py [--clients 125] [--repeats 5] [--seq-len 128]
 """
 
 import argparse
@@ -66,6 +70,8 @@ def layer_step(C):
         x = qkv.view(C, B, L, 3 * H)
         if attn.attn_route(x, HEADS) == "fused":
             att = attn.causal_attention(x, HEADS).view(C, B * L, H)
+        elif attn.attn_long_route(x, HEADS) == "long":
+            att = attn.causal_attention_long(x, HEADS).view(C, B * L, H)
         else:       # the lines of models/bert.py::encode
             x = qkv.view(C * B, L, 3, HEADS, HD).permute(2, 0, 3, 1, 4)
             att = F.scaled_dot_product_attention(x[0], x[1], x[2],
@@ -80,9 +86,12 @@ def useful(C):
     operand once per kernel that takes it (forward qkv, att, lse; backward
     qkv, att, datt, lse, dqkv), and the causal half, diagonal included, of
     the 2 forward and 5 backward products, each counted once (the kernel
-    computes S and dP in both of its backward phases)."""
+    computes S and dP in both of its backward phases).  The long kernels
+    add the row-dot pass: att and datt read, D written and read."""
     rows = C * B * L
     nbytes = rows * H * 2 * (3 + 1 + 3 + 1 + 1 + 3) + 2 * rows * HEADS * 4
+    if L > 128:
+        nbytes += rows * H * 2 * 2 + 2 * rows * HEADS * 4
     pairs = C * B * HEADS * L * (L + 1) // 2
     return nbytes, 2 * HD * pairs * (2 + 5)
 
@@ -91,7 +100,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clients", type=int, default=125)
     ap.add_argument("--repeats", type=int, default=5)
+    global B, L
+    ap.add_argument("--seq-len", type=int, default=L)
     args = ap.parse_args()
+    L = args.seq_len
+    B = max(1, 512 // L)
     C = args.clients
     step = layer_step(C)
     res = {"fused": [], "torch": []}
