@@ -19,6 +19,27 @@ from .base import (ClientBatchedModel, Params, binit, blinear, blayernorm)
 from ..ops.attn import (attn_long_route, attn_route, causal_attention,
                         causal_attention_long)
 from ..ops.head_ce import head_ce_grad, head_ce_route, head_ce_stats
+from ..ops.dense_epi import (bias_gelu, bias_residual_layernorm,
+                             dense_epi_route)
+
+
+def _dense_epi_fused(hs: torch.Tensor, params: Params, pre: str) -> bool:
+    """Whether layer ``pre``'s three epilogues (attn_out + ln1, ffn_in +
+    GELU, ffn_out + ln2) take ops/dense_epi.py's fused route, asked before
+    the layer's GEMMs run so that the other answer leaves the composed lines
+    as they are.  hs [C, N, H] is the residual; the GEMM outputs the kernels
+    will read are fresh contiguous tensors of its dtype, so hs stands in for
+    the two of its shape and an empty one-row tensor for the ffn_in output."""
+    if not hs.is_cuda:
+        return False
+    for name, ln in (("attn_out", "ln1"), ("ffn_out", "ln2")):
+        if dense_epi_route(hs, params[f"{pre}.{name}.b"], hs,
+                           params[f"{pre}.{ln}.g"],
+                           params[f"{pre}.{ln}.b"]) != "fused":
+            return False
+    b = params[f"{pre}.ffn_in.b"]
+    return dense_epi_route(hs.new_empty((hs.shape[0], 1, b.shape[-1])),
+                           b) == "fused"
 
 
 class _TiedHeadCE(torch.autograd.Function):
@@ -204,6 +225,21 @@ class BertLM(ClientBatchedModel):
                 q, k, v = qkv[0], qkv[1], qkv[2]           # [C*B, nh, L, hd]
                 att = F.scaled_dot_product_attention(q, k, v, is_causal=True)
                 att = att.transpose(1, 2).reshape(C, B * L, h)
+            if _dense_epi_fused(hs.view(C, B * L, h), params, pre):
+                # ops/csrc/dense_epi.hip: the GEMMs run without bias and one
+                # kernel adds bias (and residual) and applies GELU / LayerNorm
+                hs = bias_residual_layernorm(
+                    blinear(att, params[f"{pre}.attn_out.w"], None),
+                    params[f"{pre}.attn_out.b"], hs.view(C, B * L, h),
+                    params[f"{pre}.ln1.g"], params[f"{pre}.ln1.b"])
+                ff = bias_gelu(blinear(hs, params[f"{pre}.ffn_in.w"], None),
+                               params[f"{pre}.ffn_in.b"])
+                hs = bias_residual_layernorm(
+                    blinear(ff, params[f"{pre}.ffn_out.w"], None),
+                    params[f"{pre}.ffn_out.b"], hs,
+                    params[f"{pre}.ln2.g"], params[f"{pre}.ln2.b"])
+                hs = hs.view(C, B, L, h)
+                continue
             hs = hs + blinear(att, params[f"{pre}.attn_out.w"],
                               params[f"{pre}.attn_out.b"]).view(C, B, L, h)
             hs = blayernorm(hs, params[f"{pre}.ln1.g"], params[f"{pre}.ln1.b"])

@@ -24,6 +24,8 @@ from .lstm import lstm_layer, lstm_route
 from .attn import (attn_long_route, attn_route, causal_attention,
                    causal_attention_long)
 from .head_ce import head_ce_grad, head_ce_route, head_ce_stats
+from .dense_epi import (bias_gelu, bias_residual_layernorm,
+                        dense_epi_route)
 
 __all__ = [
     "hip_ops_available", "load_hip_ops", "fused_sgd_update",
@@ -32,5 +34,6 @@ __all__ = [
     "apply_aggregate", "cross_entropy_fwd_bwd", "lstm_layer", "lstm_route",
     "causal_attention", "attn_route", "causal_attention_long",
     "attn_long_route", "head_ce_route", "head_ce_stats",
-    "head_ce_grad",
+    "head_ce_grad", "bias_gelu", "bias_residual_layernorm",
+    "dense_epi_route",
 ]

@@ -23,7 +23,7 @@ def build(verbose: bool = True) -> str:
                 "clip.hip", "uplink_quant.hip", "server_opt.hip", "cross_entropy.hip", "groupnorm.hip", "client_conv.hip",
                 "client_conv2.hip", "conv3_wflip.hip", "client_conv5.hip", "pool2x2.hip", "transpose.hip", "layernorm.hip", "pad2d.hip",
                "replicate.hip", "lstm.hip", "attn.hip", "attn_long.hip",
-                "head_ce.hip")]
+                "head_ce.hip", "dense_epi.hip")]
     from torch.utils.cpp_extension import load
     mod_path = load(
         name="olsim_hip_ops",

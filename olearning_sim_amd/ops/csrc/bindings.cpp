@@ -611,6 +611,139 @@ std::string head_ce_route(int64_t s, bool is_bf16, bool aligned) {
   return ols_head_ce_route(s, is_bf16, aligned);
 }
 
+// ---- bias + GELU, bias + residual + LayerNorm (dense_epi.hip) --------------
+// Row operands (z, res, dy and every row output) are contiguous bf16
+// [C, N, W] on one GPU and on 16-byte boundaries, column operands (b, gamma,
+// beta) contiguous bf16 [C, W] likewise, mean and rstd fp32 [C, N]; the
+// width passes dense_epi_route.h.  Anything else is an error here, never a
+// quiet detour.  Outputs are passed in.
+
+struct DenseEpiDims {
+  int C, N, W;
+};
+
+DenseEpiDims dense_epi_dims(const char* op, const at::Tensor& z,
+                            bool layernorm,
+                            std::initializer_list<const at::Tensor*> rows,
+                            std::initializer_list<const at::Tensor*> cols,
+                            std::initializer_list<const at::Tensor*> stats) {
+  TORCH_CHECK(z.is_cuda() && z.dim() == 3, op,
+              ": the first operand must be a [C, N, W] GPU tensor, got ",
+              z.sizes());
+  const int64_t C = z.size(0), N = z.size(1), W = z.size(2);
+  TORCH_CHECK(C >= 1 && C <= 65535 && N >= 1 && N < (int64_t(1) << 31) &&
+                  W >= 1 && W < (int64_t(1) << 30),
+              op, ": C = ", C, ", N = ", N, ", W = ", W, " out of range");
+  bool aligned = true;
+  auto check = [&](const at::Tensor& t, at::IntArrayRef shape,
+                   at::ScalarType dt, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.device() == z.device() &&
+                    t.scalar_type() == dt && t.is_contiguous() &&
+                    t.sizes() == shape,
+                op, ": ", what, " on the first operand's GPU expected, got ",
+                t.sizes());
+    aligned = aligned && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  for (const at::Tensor* t : rows)
+    check(*t, {C, N, W}, at::kBFloat16, "a contiguous bf16 [C, N, W] tensor");
+  for (const at::Tensor* t : cols)
+    check(*t, {C, W}, at::kBFloat16, "a contiguous bf16 [C, W] tensor");
+  for (const at::Tensor* t : stats)
+    check(*t, {C, N}, at::kFloat, "a contiguous fp32 [C, N] tensor");
+  TORCH_CHECK(std::string(ols_dense_epi_route(W, 1, aligned, layernorm)) !=
+                  "torch",
+              op, ": width ", W, " or an operand off a 16-byte boundary is "
+              "not served (dense_epi_route)");
+  return {(int)C, (int)N, (int)W};
+}
+
+// fp32 scratch [C, row_blocks, K, W] and its reduction into cols [K, C, W]
+at::Tensor dense_epi_scratch(const at::Tensor& z, const DenseEpiDims& d,
+                             int64_t row_block, int K) {
+  TORCH_CHECK(row_block >= 1 && row_block <= 1024, "row_block in 1..1024");
+  return at::empty({d.C, ols_dense_epi_row_blocks(d.N, (int)row_block), K,
+                    d.W},
+                   z.options().dtype(at::kFloat));
+}
+
+void dense_epi_finish(const char* op, const at::Tensor& part,
+                      const at::Tensor& cols, const DenseEpiDims& d, int K) {
+  TORCH_CHECK(cols.is_cuda() && cols.device() == part.device() &&
+                  cols.scalar_type() == at::kBFloat16 &&
+                  cols.is_contiguous() &&
+                  cols.sizes() == at::IntArrayRef({K, d.C, d.W}),
+              op, ": the column sums must be contiguous bf16 [", K,
+              ", C, W], got ", cols.sizes());
+  const int rc = ols_colsum_finish(
+      part.data_ptr<float>(), cols.data_ptr(), d.C, (int)part.size(1), K, d.W,
+      at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, op, ": colsum_finish refused the operands");
+}
+
+// y <- bf16(gelu(z + b)), erf form
+void bias_gelu_fwd(at::Tensor z, at::Tensor b, at::Tensor y,
+                   int64_t row_block) {
+  const DenseEpiDims d =
+      dense_epi_dims("bias_gelu_fwd", z, false, {&z, &y}, {&b}, {});
+  TORCH_CHECK(row_block >= 1 && row_block <= 1024, "row_block in 1..1024");
+  const int rc = ols_bias_gelu_fwd(
+      z.data_ptr(), b.data_ptr(), y.data_ptr(), d.C, d.N, d.W, (int)row_block,
+      at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "bias_gelu_fwd: launcher refused the operands");
+}
+
+// dz <- bf16(dy * gelu'(z + b)), db [1, C, F] <- its column sums over N
+void bias_gelu_bwd(at::Tensor z, at::Tensor b, at::Tensor dy, at::Tensor dz,
+                   at::Tensor db, int64_t row_block) {
+  const DenseEpiDims d =
+      dense_epi_dims("bias_gelu_bwd", z, false, {&z, &dy, &dz}, {&b}, {});
+  at::Tensor part = dense_epi_scratch(z, d, row_block, 1);
+  const int rc = ols_bias_gelu_bwd(
+      z.data_ptr(), b.data_ptr(), dy.data_ptr(), dz.data_ptr(),
+      part.data_ptr<float>(), d.C, d.N, d.W, (int)row_block,
+      at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "bias_gelu_bwd: launcher refused the operands");
+  dense_epi_finish("bias_gelu_bwd", part, db, d, 1);
+}
+
+// s <- bf16(z + b + res), y <- LayerNorm(s) * gamma + beta, mean, rstd of s
+void brln_fwd(at::Tensor z, at::Tensor b, at::Tensor res, at::Tensor gamma,
+              at::Tensor beta, double eps, at::Tensor y, at::Tensor s,
+              at::Tensor mean, at::Tensor rstd) {
+  const DenseEpiDims d =
+      dense_epi_dims("brln_fwd", z, true, {&z, &res, &y, &s},
+                     {&b, &gamma, &beta}, {&mean, &rstd});
+  const int rc = ols_brln_fwd(
+      z.data_ptr(), b.data_ptr(), res.data_ptr(), gamma.data_ptr(),
+      beta.data_ptr(), y.data_ptr(), s.data_ptr(), mean.data_ptr<float>(),
+      rstd.data_ptr<float>(), d.C, d.N, d.W, (float)eps,
+      at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "brln_fwd: launcher refused the operands");
+}
+
+// ds <- the gradient of s; cols [3, C, H] <- dgamma, dbeta, db
+void brln_bwd(at::Tensor s, at::Tensor dy, at::Tensor gamma, at::Tensor mean,
+              at::Tensor rstd, at::Tensor ds, at::Tensor cols,
+              int64_t row_block) {
+  const DenseEpiDims d = dense_epi_dims("brln_bwd", s, true, {&s, &dy, &ds},
+                                        {&gamma}, {&mean, &rstd});
+  at::Tensor part = dense_epi_scratch(s, d, row_block, 3);
+  const int rc = ols_brln_bwd(
+      s.data_ptr(), dy.data_ptr(), gamma.data_ptr(), mean.data_ptr<float>(),
+      rstd.data_ptr<float>(), ds.data_ptr(), part.data_ptr<float>(), d.C, d.N,
+      d.W, (int)row_block, at::cuda::getCurrentCUDAStream().stream());
+  TORCH_CHECK(rc == 0, "brln_bwd: launcher refused the operands");
+  dense_epi_finish("brln_bwd", part, cols, d, 3);
+}
+
+// "fused" or "torch": the path a row width takes (dense_epi_route.h), given
+// the dtype and whether every operand is contiguous and on a 16-byte boundary
+std::string dense_epi_route(int64_t width, bool is_bf16, bool aligned,
+                            bool layernorm) {
+  TORCH_CHECK(width >= 0, "dense_epi_route: width >= 0");
+  return ols_dense_epi_route(width, is_bf16, aligned, layernorm);
+}
+
 std::tuple<at::Tensor, at::Tensor> cross_entropy_fwd_bwd(at::Tensor logits,
                                                          at::Tensor labels) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous());
@@ -1357,6 +1490,17 @@ TORCH_LIBRARY(olsim_hip, m) {
         "-> ()");
   m.def("head_ce_route(int s, bool is_bf16, bool aligned) -> str",
         &head_ce_route);
+  m.def("bias_gelu_fwd(Tensor z, Tensor b, Tensor(a!) y, int row_block) "
+        "-> ()");
+  m.def("bias_gelu_bwd(Tensor z, Tensor b, Tensor dy, Tensor(a!) dz, "
+        "Tensor(b!) db, int row_block) -> ()");
+  m.def("brln_fwd(Tensor z, Tensor b, Tensor res, Tensor gamma, Tensor beta, "
+        "float eps, Tensor(a!) y, Tensor(b!) s, Tensor(c!) mean, "
+        "Tensor(d!) rstd) -> ()");
+  m.def("brln_bwd(Tensor s, Tensor dy, Tensor gamma, Tensor mean, "
+        "Tensor rstd, Tensor(a!) ds, Tensor(b!) cols, int row_block) -> ()");
+  m.def("dense_epi_route(int width, bool is_bf16, bool aligned, "
+        "bool layernorm) -> str", &dense_epi_route);
   m.def("cross_entropy_fwd_bwd(Tensor logits, Tensor labels) -> (Tensor, Tensor)");
   m.def("groupnorm_fwd(Tensor x, Tensor res, Tensor gamma, Tensor beta, "
         "int clients, int groups, float eps, bool relu) -> (Tensor, Tensor, Tensor)");
@@ -1422,6 +1566,10 @@ TORCH_LIBRARY_IMPL(olsim_hip, CUDA, m) {
   m.impl("attn_long_bwd", &attn_long_bwd);
   m.impl("head_ce_stats", &head_ce_stats);
   m.impl("head_ce_grad", &head_ce_grad);
+  m.impl("bias_gelu_fwd", &bias_gelu_fwd);
+  m.impl("bias_gelu_bwd", &bias_gelu_bwd);
+  m.impl("brln_fwd", &brln_fwd);
+  m.impl("brln_bwd", &brln_bwd);
   m.impl("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.impl("groupnorm_fwd", &groupnorm_fwd);
   m.impl("groupnorm_bwd", &groupnorm_bwd);

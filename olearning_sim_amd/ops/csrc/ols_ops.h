@@ -141,6 +141,36 @@ extern "C" int ols_head_ce_grad(const void* logits, void* out,
 extern "C" const char* ols_head_ce_route(int64_t s, int is_bf16,
                                          int aligned);
 
+// dense_epi.hip: what follows a bias-free GEMM of a BertLM encoder layer.
+// z, y, dy, dz, res, s, ds [C, N, W] bf16; b, gamma, beta [C, W] bf16; mean,
+// rstd [C, N] fp32.  part is fp32 scratch [C, row_blocks, K, W] with
+// row_blocks = ols_dense_epi_row_blocks(N, row_block) and K = 1 (GELU) or 3
+// (LayerNorm: dgamma, dbeta, db); ols_colsum_finish reduces it to a bf16
+// [K, C, W].  All return 1 and launch nothing where dense_epi_route.h says
+// "torch" (a width, or a pointer off a 16-byte boundary) or a size is out of
+// range.
+extern "C" int ols_bias_gelu_fwd(const void* z, const void* b, void* y, int C,
+                                 int N, int F, int row_block,
+                                 hipStream_t stream);
+extern "C" int ols_bias_gelu_bwd(const void* z, const void* b, const void* dy,
+                                 void* dz, float* part, int C, int N, int F,
+                                 int row_block, hipStream_t stream);
+extern "C" int ols_brln_fwd(const void* z, const void* b, const void* res,
+                            const void* gamma, const void* beta, void* y,
+                            void* s, float* mean, float* rstd, int C, int N,
+                            int H, float eps, hipStream_t stream);
+extern "C" int ols_brln_bwd(const void* s, const void* dy, const void* gamma,
+                            const float* mean, const float* rstd, void* ds,
+                            float* part, int C, int N, int H, int row_block,
+                            hipStream_t stream);
+extern "C" int ols_colsum_finish(const float* part, void* out, int C,
+                                 int row_blocks, int K, int W,
+                                 hipStream_t stream);
+extern "C" int ols_dense_epi_row_blocks(int N, int row_block);
+// "fused" or "torch" (dense_epi_route.h)
+extern "C" const char* ols_dense_epi_route(int64_t width, int is_bf16,
+                                           int aligned, int layernorm);
+
 extern "C" void ols_cross_entropy_fwd_bwd(
     const void* logits, const int64_t* labels, float* loss, void* dlogits,
     int64_t nrows, int64_t K, float inv_n, int dtype, hipStream_t stream);
